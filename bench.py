@@ -9,9 +9,21 @@ metric is quoted on: single-centre Lennard-Jones, rho*=0.785302672, rc=2.5 sigma
 N = 2*368^3 = 99 672 064 (the "10^8" box), which fits ONE MI355X; `--gpus N` splits that SAME box over N GPUs (strong
 scaling, regular rank grid, RCCL ghost-cell halo).  `--n-per-dim 171` gives the 10^7 variant (configs[1]).  The start
 configuration is generated in device memory and is resident in HBM before the timed region.  Prints ONE JSON line
-(rank 0) with `roofline` (force kernel: algorithmic bytes / HIP-event kernel time vs 8 TB/s) and `cpu_baseline` (the
-REAL reference binary oracle/_ref/MarDyn timed on the host cores on a bounded sample of the same workload; the oracle
-restatement is used only if that binary is absent).
+(rank 0).
+
+A plain run does only what the headline figure needs: set-up, the melt phase that defines the timed state, W warm-up steps,
+the K timed steps, the outputs of `--dump-outputs DIR` and the result line (`roofline`: force kernel, algorithmic bytes /
+HIP-event kernel time of the timed launches vs 8 TB/s).  `--full` adds everything else the benchmark measures or checks:
+the start-up check of an N > 1 run against the single domain, the lattice-start figure, per-phase device times
+(profiling steps after the timed window), the 200-step `long_run` / `steady_state_value`, the live rocprofv3 counter
+passes behind `roofline.traffic` / `roofline.compute`, and `cpu_baseline` (the REAL reference binary oracle/_ref/MarDyn
+timed on the host cores on a bounded sample of the same workload; the oracle restatement is used only if that binary is
+absent).  `--no-cpu-baseline`, `--no-live-pmc` and `--long-run 0` switch single legs of `--full` off.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float64): `globals` (the
+run's return value: U_pot, virial, sum m v^2, sum I w^2, N, rotational DOF) and, sorted by molecule id, `ids`, `r`, `v`,
+`F` (multi-site workloads: `q`, `D`, `M` too) — all molecules, or above DUMP_BYTES a fixed sample chosen by a hash of the
+molecule id.  The start configuration depends on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -43,6 +55,8 @@ MS_FORCE_BYTES_PER_MOLECULE = 104.0  # multi-site force pass: read r 24 + q 32, 
 # reach HBM and the 256 B integrator pass disappears
 MS_FUSED_BYTES_PER_MOLECULE = 208.0
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 48 << 20               # --dump-outputs: size of the per-molecule arrays of one rank (all ranks together: same bound)
+DUMP_HASH = 0x9E3779B97F4A7C15      # --dump-outputs: multiplicative hash of the molecule id that picks the sample
 BASELINE_METRIC = "particle-updates/sec (whole node), 10^8 LJ liquid Argon, rc=2.5\u03c3"  # BASELINE.json, verbatim
 
 
@@ -428,6 +442,56 @@ def live_pmc_compute(argv_tail, avg_launch_s, budget_s=300):
     return out, kernel
 
 
+def dump_outputs(dirname, e, last, world, rank, rotation):
+    """--dump-outputs: the arrays a caller of the timed path receives after its last step — the run's global values and the state +
+    forces the engine hands back — as float64 .npy files, rows sorted by molecule id (the device order is the engine's own business).
+    Above DUMP_BYTES a fixed sample: the molecules whose hashed id falls below a threshold (a function of the id alone, so every
+    build and every rank picks the same molecules).  rotation: orientation, angular momentum and torque too (multi-site sets)."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else f".rank{rank}"
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if isinstance(last, dict) and rank == 0:
+        np.save(os.path.join(dirname, "globals.npy"),
+                np.array([last.get(k, np.nan) for k in ("upot", "virial", "summv2", "sumIw2", "n", "rot_dof")], dtype=np.float64))
+    capi = importlib.import_module("ls1-mardyn_amd.capi")
+    ids = e.download_ids()
+    n = len(ids)
+    row_bytes = 8 * (1 + 3 + 3 + 3 + (4 + 3 + 3 if rotation else 0))
+    rows = DUMP_BYTES // world // row_bytes
+    if n > rows:
+        h = (ids * np.uint64(DUMP_HASH)) >> np.uint64(32)  # the product wraps mod 2^64: bits 32-63 of it
+        sel = np.flatnonzero(h < np.uint64(int(0.98 * rows / n * 2.0 ** 32)))  # ~0.98 rows +- sqrt(rows): below DUMP_BYTES
+    else:
+        sel = np.arange(n)
+    sel = sel[np.argsort(ids[sel], kind="stable")]
+    save("ids", ids[sel])
+    del ids
+
+    # one column at a time: at 10^8 molecules every full column is 2.4 GB of host memory
+    def state(col, width):
+        a = np.zeros((n, width))
+        ptrs = [capi.dptr(a) if c == col else None for c in ("r", "v", "q", "D")]
+        e._chk(e.lib.ls1hip_download_state(e.ctx, n, None, None, *ptrs))
+        return a[sel]
+
+    def force(col):
+        a = np.zeros((n, 3))
+        ptrs = [capi.dptr(a) if c == col else None for c in ("F", "M", "Vi")]
+        e._chk(e.lib.ls1hip_download_forces(e.ctx, n, *ptrs))
+        return a[sel]
+
+    save("r", state("r", 3))
+    save("v", state("v", 3))
+    save("F", force("F"))
+    if rotation:
+        save("q", state("q", 4))
+        save("D", state("D", 3))
+        save("M", force("M"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -452,11 +516,17 @@ def main():
     ap.add_argument("--loopback", action="store_true",
                     help="diagnostic (with --decomp): route the local periodic images through the RCCL transport "
                          "(send/recv to the own rank): the full multi-GPU exchange path on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure too: start-up check of an N > 1 run, lattice-start figure, per-phase "
+                         "device times, the long window, live counter passes, CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64; "
+                         "per-molecule arrays sorted by id, a fixed id-hash sample above 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--local-rebuild", type=int, default=-1, choices=[-1, 0, 1],
                     help="diagnostic: 0 = rebuild the lists by the global displacement bound instead of the brick-neighbourhood one")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="skip the two short rocprofv3 --pmc child passes that measure roofline.traffic live (the figure "
+                    help="with --full: skip the two short rocprofv3 --pmc child passes that measure roofline.traffic live (the figure "
                          "of the committed profiles/ summary is reported instead)")
     ap.add_argument("--workload", choices=("lj", "ethane", "mixed"), default="lj",
                     help="lj = the metric's 1CLJ liquid (default); ethane = BASELINE configs[3]: the reference's equilibrated 2CLJ "
@@ -467,7 +537,7 @@ def main():
                     help="untimed device steps BEFORE the warm-up steps (lj workload: default 200 — the lattice start melts, list "
                          "lengths spread; the timed window is then steady state)")
     ap.add_argument("--long-run", type=int, default=200,
-                    help="lj workload, one GPU: steps of the secondary long window after the timed one (0 = none)")
+                    help="with --full, lj / ethane workload, one GPU: steps of the secondary long window after the timed one (0 = none)")
     ap.add_argument("--no-align", action="store_true",
                     help="lj workload: do not place the timed window in the list lifetime (default: the melt phase is extended by a few "
                          "steps so that the K timed steps hold round(K * builds-per-step) list rebuilds, see config.timed_window)")
@@ -491,7 +561,7 @@ def main():
         # time the same physical state
         args.melt = 200 if args.workload == "lj" else 0
     if args.pmc_child:  # a counter pass: the same workload, a few steps, nothing else
-        args.steps, args.warmup, args.no_cpu_baseline, args.no_live_pmc = 6, 2, True, True
+        args.steps, args.warmup, args.full, args.dump_outputs = 6, 2, False, None
     if args.workload != "lj":
         if args.gpus != 1 or args.decomp:
             sys.exit("bench.py --workload ethane|mixed runs on one GPU (multi-site lists serve single-rank domains)")
@@ -534,7 +604,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         decomp = importlib.import_module("ls1-mardyn_amd.decomp")
-        self_check = multi_gpu_self_check(comps, world, rank, local_rank, rehearse, torch, dist) if world > 1 and not args.pmc_child else None
+        self_check = multi_gpu_self_check(comps, world, rank, local_rank, rehearse, torch, dist) if world > 1 and args.full else None
         sim = decomp.build_strong_scaling_box(comps, RC, n, world, rank, local_rank, rho=RHO, temp=TEMP,
                                               cic=args.cic or None, kernel=args.kernel, stage_through_host=rehearse,
                                               loopback=args.loopback,
@@ -624,16 +694,19 @@ def main():
     melt_tail = None  # (list builds, steps) over the second half of the melt phase: the rebuild rate of the melted liquid
     if args.melt:
         if args.workload == "lj" and not args.pmc_child and args.melt >= 60:
-            # secondary figure, for continuity with earlier rounds (which timed the lattice start): 10 + 30 of the melt steps are
-            # timed as they go by — NOT the headline
+            # secondary figure (--full), for continuity with earlier rounds (which timed the lattice start): 10 + 30 of the melt
+            # steps are timed as they go by — NOT the headline.  (A plain run makes the same calls, so that the timed state does
+            # not depend on --full: the last step of every run() call is an unfused one.)
             run(10)
-            sync()
+            if args.full:
+                sync()
             t_l = time.perf_counter()
             run(30)
-            sync()
-            lattice = {"steps": 30, "ms_per_step": (time.perf_counter() - t_l) / 30 * 1e3,
-                       "note": "steps 11-40 after the jittered-lattice start (what rounds 1-2 quoted); the headline `value` is the "
-                               "steady state after the melt phase"}
+            if args.full:
+                sync()
+                lattice = {"steps": 30, "ms_per_step": (time.perf_counter() - t_l) / 30 * 1e3,
+                           "note": "steps 11-40 after the jittered-lattice start (what rounds 1-2 quoted); the headline `value` is the "
+                                   "steady state after the melt phase"}
             rest = args.melt - 40
             run(rest // 2)
             eb = sim.engine if sim is not None else eng
@@ -682,15 +755,19 @@ def main():
     builds_in_window = (int(e.get_option("verlet_builds")) - builds_before) if builds_before is not None else None
     e.timing_enable(0)
     force_ms, force_n = e.timing("force")
-    # per-phase device times: a few extra steps with every phase timed, OUTSIDE the timed region
-    e.timing_reset()
-    e.timing_enable(1)
-    nprof = max(2, min(10, args.steps))
-    run(nprof)
-    sync()
-    e.timing_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, last, world, rank, rotation=args.workload != "lj")
+    nprof = 0
+    if args.full:
+        # per-phase device times: a few extra steps with every phase timed, OUTSIDE the timed region
+        e.timing_reset()
+        e.timing_enable(1)
+        nprof = max(2, min(10, args.steps))
+        run(nprof)
+        sync()
+        e.timing_enable(0)
     long_run = None
-    if args.workload in ("lj", "ethane") and world == 1 and not args.pmc_child and args.long_run > 0:  # (mixed: bounded window, see MIXED_DT)
+    if args.full and args.workload in ("lj", "ethane") and world == 1 and args.long_run > 0:  # (mixed: bounded window, see MIXED_DT)
         # secondary figure: a window long enough to average over the list lifetimes.  A rebuild step costs ~3 ordinary steps and comes
         # every ~11 steps, so a K-step window holds floor or ceil of K / 10.8 of them: +- 2 % on 50 steps, +- 5 % on the driver's 20
         b0 = int(e.get_option("verlet_builds"))
@@ -717,10 +794,11 @@ def main():
         t[dist.get_rank()] = int(e.count()[0])
         dist.all_reduce(t)
         per_rank = [int(x) for x in t.tolist()]
-    integ_ms, _ = e.timing("integrate")
-    rebin_ms, _ = e.timing("rebin")
-    halo_ms, _ = e.timing("halo")
-    build_ms, build_n = e.timing("build")
+    if nprof:
+        integ_ms, _ = e.timing("integrate")
+        rebin_ms, _ = e.timing("rebin")
+        halo_ms, _ = e.timing("halo")
+        build_ms, build_n = e.timing("build")
     n_local = e.count()[0]
     # HBM traffic of the force kernel from rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE), taken
     # offline on this exact workload and committed under profiles/ (PMC collection cannot run inside the timed loop)
@@ -755,7 +833,7 @@ def main():
         traffic = None
     traffic_source = f"profiles/{PMC_SUMMARY} (rocprofv3 --pmc passes of this workload, committed)" if traffic is not None else None
     live_compute = None
-    if rank == 0 and world == 1 and not args.no_live_pmc and not args.decomp:
+    if args.full and rank == 0 and world == 1 and not args.no_live_pmc and not args.decomp:
         tail = ["--n-per-dim", str(n), "--skin", str(args.skin), "--kernel", str(args.kernel), "--cic", str(args.cic),
                 "--split", str(args.split), "--workload", args.workload, "--melt", str(min(args.melt, 40)),
                 "--precision", args.precision] + (["--no-fuse"] if args.no_fuse else []) + \
@@ -820,15 +898,19 @@ def main():
                          "avg_launch_ms": avg_force_s * 1e3, "launches": int(force_n),
                          "algorithmic_bytes_per_launch": alg_bytes_per_launch,
                          "full_step_frac": step_bytes_total / elapsed / 1e9 / HBM_PEAK_GBS},
-            "device_ms_per_step": {"force": force_ms / args.steps, "integrate": integ_ms / nprof,
-                                   "rebin": rebin_ms / nprof, "halo": halo_ms / nprof, "list_build": build_ms / nprof,
-                                   "list_build_ms_per_build": (build_ms / build_n if build_n else None),
+            "device_ms_per_step": {"force": force_ms / args.steps,
                                    "list_builds_per_step": (e.get_option("verlet_builds") / max(e.get_option("verlet_steps"), 1)
                                                             if e.get_option("verlet_lists") else 0.0),
-                                   "note": "force: mean over the timed steps; the other phases: mean over the profiling steps "
-                                           "after the timed window (rebuild steps included at their frequency)"},
+                                   "note": "force: mean over the timed steps; the other phases (--full only): mean over the profiling "
+                                           "steps after the timed window (rebuild steps included at their frequency)"},
             "last_step": {k: (float(v_) if not isinstance(v_, int) else v_) for k, v_ in last.items()} if isinstance(last, dict) else None,
         }
+        if nprof:
+            out["device_ms_per_step"].update({"integrate": integ_ms / nprof, "rebin": rebin_ms / nprof, "halo": halo_ms / nprof,
+                                              "list_build": build_ms / nprof,
+                                              "list_build_ms_per_build": (build_ms / build_n if build_n else None)})
+        if window:
+            out["config"]["timed_window"] = window
         if lattice is not None:
             lattice["value"] = n_total / (lattice["ms_per_step"] * 1e-3)
             out["lattice_start"] = lattice
@@ -859,10 +941,11 @@ def main():
             out["roofline"]["compute"] = comp
         if world > 1:
             out["rccl_world_size"] = world_seen
-            out["multi_gpu_self_check"] = self_check
+            if self_check is not None:
+                out["multi_gpu_self_check"] = self_check
             out["config"]["molecules_per_gpu_by_rank"] = per_rank
             out["config"]["transport"] = "gloo staged through the host (rehearsal)" if rehearse else "RCCL (torch.distributed nccl backend)"
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(workload=args.workload)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         sys.stdout.flush()

@@ -96,7 +96,7 @@ def test_bench_py_launched_as_the_driver_launches_it_with_two_ranks():
     env = dict(os.environ, LS1_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
-           "--n-per-dim", str(n), "--melt", "0", "--no-live-pmc", "--no-cpu-baseline"]
+           "--n-per-dim", str(n), "--melt", "0", "--full", "--no-live-pmc", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

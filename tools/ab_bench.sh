@@ -10,7 +10,7 @@ flags="${@:---steps 60 --warmup 10}"
 for rep in 1 2; do
   for t in "${tags[@]}"; do
     lib=""; [ "$t" != "base" ] && lib="ls1-mardyn_amd/lib/variants/libls1hip_$t.so"
-    LS1HIP_LIB=$lib python bench.py --no-cpu-baseline --no-live-pmc $flags 2>/dev/null | python -c "
+    LS1HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-live-pmc $flags 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 m = d['device_ms_per_step']

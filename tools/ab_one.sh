@@ -2,7 +2,7 @@
 # one bench run of a library variant, one summary line: tools/ab_one.sh <tag|base> [bench flags]
 t=$1; shift
 lib=""; [ "$t" != "base" ] && lib="ls1-mardyn_amd/lib/variants/libls1hip_$t.so"
-LS1HIP_LIB=$lib python bench.py --no-cpu-baseline --no-live-pmc "$@" 2>/dev/null | python -c "
+LS1HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-live-pmc "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 m = d['device_ms_per_step']

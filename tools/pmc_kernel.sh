@@ -6,7 +6,7 @@ K=$1; OUT=$2; shift; shift
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 cd "$REPO"
-ARGS="--steps 12 --warmup 3 --no-cpu-baseline --no-live-pmc $*"
+ARGS="--steps 12 --warmup 3 --full --no-cpu-baseline --no-live-pmc $*"
 D=$REPO/gpurun_out/pmck_tmp
 rm -rf "$D"; mkdir -p "$D"
 for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \

@@ -3,7 +3,7 @@
 out=$1; shift
 : > $out
 for s in "$@"; do
-  python bench.py --no-cpu-baseline --no-live-pmc --skin $s --steps 60 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-live-pmc --skin $s --steps 60 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 m = d['device_ms_per_step']
