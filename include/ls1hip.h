@@ -329,6 +329,45 @@ int ls1hip_run(ls1hip_ctx* ctx, double dt, unsigned long nsteps, double* out6);
  * computed (unfused NVE steps before the last).  rows may be NULL to query *nrows. */
 int ls1hip_run_log(ls1hip_ctx* ctx, size_t cap_rows, double* rows, size_t* nrows);
 
+/* ---- radial distribution functions ------------------------------------------------------------------------------
+ * The reference's RDF plugin (io/RDF.{h,cpp}) and its RDFCellProcessor (particleContainer/adapter/RDFCellProcessor.cpp): a
+ * second traversal of the linked cells that counts every molecule pair inside the cutoff r_c (the force cutoff, not r_c + skin)
+ * into histograms over the centre distance, and with site_rdf the site-site distances of multi-site pairs as well.
+ * Histogram layout (u64 words):
+ *   mol[p][bin]   p runs over the component pairs (i, j >= i) in the order of RDF::collectRDF (RDF.cpp:235-241):
+ *                 (0,0) (0,1) ... (0,C-1) (1,1) ... (C-1,C-1); bin = floor(sqrt(dd) / interval_length) (RDF.h:138-146);
+ *   site          the blocks of the pairs with n_i + n_j > 2 sites (RDF.cpp:111-135), in the same order, each [m][n][bin] with m
+ *                 a site of component i and n one of component j, sites ordered LJ centres, charges, dipoles, quadrupoles
+ *                 (FullMolecule.h:171-185).  For i == j and m != n the raw counts carry the reference's double count
+ *                 (RDF.h:152-170); its writer applies the factor 1/2 (RDF.cpp:558).
+ * Every unordered pair is counted once in the sum over all ranks: the rank that owns the molecule with the smaller id counts it
+ * (the reference's cell-index rule, RDFCellProcessor.cpp:104-109, serves the same end).  A molecule and its own periodic image
+ * are not a pair: boxes are at least 2 r_c long per periodic dimension.  The grid has one cell per cutoff (cells_in_cutoff = 1).
+ *
+ * ls1hip_rdf_config: RDF::readXML + RDF::init (RDF.cpp:35-179) — bins, intervallength; site_rdf != 0 allocates the site blocks
+ *   (the reference switches them on whenever a pair has more than two sites).  Needs components and domain; bins > 0,
+ *   interval_length > 0, finite bins * interval_length.  bins = 0: sampling off, buffers freed.  Histograms start at zero. */
+int ls1hip_rdf_config(ls1hip_ctx* ctx, int bins, double interval_length, int site_rdf);
+/* Words of the two histograms of the current configuration (0, 0 when off). */
+int ls1hip_rdf_layout(const ls1hip_ctx* ctx, size_t* mol_words, size_t* site_words);
+/* One traversal (RDF::afterForces -> ParticleContainer::traverseCells(RDFCellProcessor), RDF.cpp:573-581): adds the pairs of the
+ * CURRENT positions and orientations, wherever the engine keeps them, to the device histograms, the owned molecules per component
+ * to the counters (RDF::accumulateNumberOfMolecules, RDF.cpp:195-199) and 1 to the sample counter (tickRDF).  Preconditions of
+ * ls1hip_forces(ctx, 0, ...): molecules binned, halo valid — after rebin; halo[; forces], and between two builds of the neighbour
+ * lists after ls1hip_update / ls1hip_halo_refresh (bins stale by at most skin / 2, grid sized by r_c + skin: no pair inside r_c
+ * is missed).  Anything else is an error, never a partial count.  Timer "rdf". */
+int ls1hip_rdf_sample(ls1hip_ctx* ctx);
+/* LOCAL counts of this rank (the inputs of RDF::collectRDF, RDF.cpp:231-306, which sums them over the ranks); any pointer may be
+ * NULL; n_per_component[ncomp]; *samples = traversals since the last reset. */
+int ls1hip_rdf_read(ls1hip_ctx* ctx, uint64_t* mol, size_t cap_mol, uint64_t* site, size_t cap_site, uint64_t* n_per_component,
+					uint64_t* samples);
+/* RDF::reset (RDF.cpp:309-340): histograms, molecule counters and sample counter back to zero. */
+int ls1hip_rdf_reset(ls1hip_ctx* ctx);
+/* Option "rdf_every" (ls1hip_set_option, default 0 = never): ls1hip_run samples on every step s with s % rdf_every == 0, s counted
+ * from 1 over all ls1hip_run calls of the context (simstep % _samplingFrequency of RDF::afterForces).  The pass runs on the
+ * positions of that step's force evaluation, directly before the force pass, on the step's regenerated or refreshed halo; the
+ * trajectory does not change. */
+
 /* ---- multi-GPU plumbing: packed buffers a host transport (RCCL via torch.distributed, MPI, ...) moves ---------
  * Wire formats (little endian, FP64): leaving molecule = 15 doubles {id(as bits), cid(as bits), r3, v3, q4, D3}
  * (the reference's 116-byte record, parallel/CommunicationBuffer.cpp:131-145, padded to 120); halo molecule =
@@ -369,7 +408,8 @@ int ls1hip_soa_forces(ls1hip_ctx* ctx, const int cell_dims[3], const uint32_t* c
 /* ---- measurement ---------------------------------------------------------------------------------------------- */
 
 /* Device time (ms, HIP events on the context's compute stream) and launch count accumulated per kernel class
- * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction)}. */
+ * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction),
+ * "rdf" (RDF sampling pass)}. */
 int ls1hip_timing(ls1hip_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int ls1hip_timing_reset(ls1hip_ctx* ctx);
 /* Per-launch HIP-event timing: 0 = off, 1 = every phase, 2 = force passes only (each timed scope puts two event markers

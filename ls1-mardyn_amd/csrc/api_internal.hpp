@@ -1,4 +1,4 @@
-// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing;
+// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling;
 // api_step.hip: the pieces of a time step, neighbour lists, ls1hip_run; api_exchange.hip: long-range correction, export / import of
 // the multi-rank exchange, seam A).  Round 4: split out of one 2 400-line api.hip; nothing here is exported from the
 // library (LS1_INTERNAL = hidden visibility).
@@ -142,3 +142,5 @@ LS1_INTERNAL HaloArgs halo_args(ls1hip_ctx* c);
 LS1_INTERNAL int do_rebin_finish(ls1hip_ctx* c, uint32_t n_in);
 LS1_INTERNAL void macro_to_upot_virial(const DevCounters* h, double* upot, double* virial);
 LS1_INTERNAL int materialise_positions(ls1hip_ctx* c);
+LS1_INTERNAL int rdf_sample_impl(ls1hip_ctx* c);  // api_rdf.hip: one RDF traversal (ls1hip_rdf_sample; ls1hip_run with "rdf_every")
+LS1_INTERNAL void rdf_destroy(ls1hip_ctx* c);

@@ -965,6 +965,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	if (!c) return LS1HIP_EINVAL;
 	REQUIRE(c, !c->has_remote, "ls1hip_run drives single-rank domains only (use the piecewise calls with a transport)");
 	REQUIRE(c, c->forces_valid, "initial forces required (rebin, halo, forces) before ls1hip_run");
+	REQUIRE(c, !c->opt_rdf_every || c->rdf_bins > 0, "option rdf_every is set but RDF sampling is not configured (ls1hip_rdf_config)");
 	HIPCHK(c, hipSetDevice(c->device));
 	// Between two steps of an NVE run on the LJ fast path the force pass does the integration itself (fused mode, the
 	// reference's reduced-memory scheme); the last step is unfused so that F and the kinetic sums are available.
@@ -1007,17 +1008,25 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			if ((rc = ls1hip_kick_then_kick_drift(c, dt))) return rc;
 		}
 		advanced = fuse && s + 1 < nsteps;
+		// RDF::afterForces (RDF.cpp:573-581): simstep % samplingfrequency == 0 samples the positions of this step's force evaluation.
+		// The pass runs directly BEFORE the force pass (a fused pass leaves the next step's positions behind), on the refreshed
+		// or regenerated halo; nothing of the step itself changes.
+		const unsigned long simstep = ++c->run_step;
+		const bool rdf_now = c->opt_rdf_every > 0 && simstep % (unsigned long)c->opt_rdf_every == 0;
 		if (verlet) {
 			// the lists, the binning and the halo slots live until the displacement bound of the molecules (accumulated on
 			// the device by whichever pass drifts them) exceeds skin / 2; then re-bin, regenerate the halo, rebuild the lists
 			if ((rc = ls1hip_update(c, nullptr))) return rc;
+			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			// unfused steps (the last one; every step of an NVT run): the pass still does the post-force kick + sum m v^2
 			rc = advanced ? ls1hip_forces_list(c, 0, dt, nullptr, nullptr)
 						  : forces_list_impl(c, 0, list_kick ? dt : 0., list_kick, nullptr, nullptr);
-		} else if (c->opt_overlap_halo == 2) {
+		} else if (c->opt_overlap_halo == 2 || (c->opt_overlap_halo && rdf_now)) {
 			if ((rc = ls1hip_rebin(c))) return rc;
-			// halo first, then the inner and the boundary cells as two passes of the same stream
+			// halo first, then the inner and the boundary cells as two passes of the same stream (also the order of a sampling
+			// step of mode 1: the RDF pass needs the halo before the first force pass moves anything)
 			if ((rc = ls1hip_halo(c))) return rc;
+			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 1, dt, nullptr, nullptr) : ls1hip_forces(c, 1, nullptr, nullptr);
 			if (rc) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 2, dt, nullptr, nullptr) : ls1hip_forces(c, 2, nullptr, nullptr);
@@ -1031,6 +1040,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		} else {
 			if ((rc = ls1hip_rebin(c))) return rc;
 			if ((rc = ls1hip_halo(c))) return rc;
+			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 0, dt, nullptr, nullptr) : ls1hip_forces(c, 0, nullptr, nullptr);
 		}
 		if (rc) return rc;

@@ -153,6 +153,20 @@ struct BrickLists {
 	uint32_t n[5] = {0, 0, 0, 0, 0};
 };
 
+// radial distribution functions (kernels_rdf.hip): io/RDF.h:111-170, adapter/RDFCellProcessor.cpp
+constexpr int RDF_MAXPAIRS = MAXC * (MAXC + 1) / 2;
+struct RdfParams {
+	int bins, ncomp;
+	double dr, maxd2, rc2;  // bin width, (bins * dr)^2 as RDF::init forms it (RDF.cpp:47), rc^2 (RDFCellProcessor.h)
+	int nsites[MAXC];
+	uint32_t site_off[RDF_MAXPAIRS];  // word offset of the component pair's [m][n][bin] block, 0xffffffff = none (n_i + n_j <= 2)
+	uint32_t mol_words, site_words;
+	int mol_lds, site_lds;  // histogram kept in LDS per workgroup (else global atomics): the budget rule of launch_rdf
+	const uint64_t* id;     // molecule ids, owned + halo segment
+	const uint32_t* hsrc;   // per halo slot: owned index of its source molecule (0xffffffff: imported record)
+	unsigned long long *g_mol, *g_site, *g_n;  // global histograms, owned molecules per component
+};
+
 struct Timer {
 	std::vector<hipEvent_t> ev;  // start/stop pairs
 	size_t used = 0;
@@ -281,6 +295,15 @@ struct ls1hip_ctx {
 	double* d_steplog = nullptr;
 	double *log_row = nullptr, *log_row_kin = nullptr;  // rows the next force / kinetic reduction refreshes (null outside ls1hip_run)
 	size_t steplog_steps = 0;
+	// radial distribution functions (ls1hip_rdf_*; kernels_rdf.hip): one device buffer {mol words, site words, MAXC counters}
+	int rdf_bins = 0, rdf_site = 0;
+	double rdf_dr = 0.;
+	unsigned long long* d_rdf = nullptr;
+	size_t rdf_mol_words = 0, rdf_site_words = 0;
+	uint64_t rdf_samples = 0;
+	long opt_rdf_every = 0;
+	unsigned long run_step = 0;  // steps ls1hip_run has done on this context (simstep of RDF::afterForces)
+	ls1::Timer t_rdf;
 	// streaming upload (ls1hip_upload_begin / _chunk / _records / _end)
 	bool ingest_open = false;
 	size_t ingest_total = 0, ingest_at = 0;
@@ -415,6 +438,8 @@ void launch_msl_fill(const ForceParams& p, const uint32_t* off, const uint32_t* 
 					 uint8_t* out_il, int ncomp, const uint32_t* scratch, const uint16_t* mcnt, uint32_t stride, hipStream_t s);
 bool launch_force_ms_list(const ForceParams& p, bool has_rot, bool lj_only, bool linear, int ncomp, const uint32_t* off, const uint32_t* pj, const uint8_t* pil,
 						  const double* shift27, double* pk, hipStream_t s, uint32_t* nblocks, size_t partials_cap, bool pk_fresh = false);
+// RDF sampling pass over all bricks (kernels_rdf.hip); fills r.mol_lds / r.site_lds; false: the grid cannot be served (hw != 1)
+bool launch_rdf(const ForceParams& p, RdfParams r, bool has_rot, double mean_per_cell, hipStream_t s);
 // kin_in_slot1: the partials' slot 1 carries sum m v^2 of a fused force + integration pass (goes to cnt->kin[0], not to
 // the macroscopic sums); log (may be null): the step-log row {U_pot, virial, sum m v^2, sum I w^2, N, rotDOF} to refresh
 struct ReduceMode {

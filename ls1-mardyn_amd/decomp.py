@@ -442,6 +442,37 @@ class DistributedSimulation:
                     rot_dof=int(v[5]))
 
 
+def rdf_collect(engine, dist=None, group=None, device=None):
+    """RDF::collectRDF (io/RDF.cpp:231-306): the local histograms and molecule counters of every rank summed by ONE all-reduce
+    (int64; the reference sends one collective per block).  Returns the dict of DeviceEngine.rdf_read with global values;
+    `samples` is this rank's own (every rank ticks the same steps).  Without an initialised process group: the local values."""
+    local = engine.rdf_read()
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    parts = [local["mol"].reshape(-1)] + [b.reshape(-1) for b in local["site"]] + [local["n_per_component"]]
+    flat = np.concatenate(parts).astype(np.int64)
+    t = torch.from_numpy(flat)
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    flat = t.cpu().numpy().astype(np.uint64)
+    out, at = dict(local), 0
+    n = local["mol"].size
+    out["mol"] = flat[at:at + n].reshape(local["mol"].shape)
+    at += n
+    site = []
+    for b in local["site"]:
+        site.append(flat[at:at + b.size].reshape(b.shape))
+        at += b.size
+    out["site"] = site
+    out["n_per_component"] = flat[at:at + local["n_per_component"].size].copy()
+    return out
+
+
 def build_strong_scaling_box(comps, rc, n_per_dim, world, rank, local_rank, rho, temp, cic=None, kernel=0,
                              stage_through_host=False, loopback=False, options=None, skin=None):
     """bench.py helper: the GLOBAL jittered bcc liquid of 2*n^3 molecules (synth.py) split over the rank grid; every

@@ -24,6 +24,8 @@ class DeviceEngine:
         self.device = device
         self.rc = None
         self.has_rot = False
+        self.n_sites = []
+        self.rdf_bins = 0
 
     # -- lifetime ---------------------------------------------------------------------------------------------------
     def close(self):
@@ -63,6 +65,7 @@ class DeviceEngine:
             # an I line that overrides a zero site moment: the reference keeps counting the site-derived degrees of freedom
             self._chk(self.lib.ls1hip_set_rot_dof(self.ctx, int(f["ncomp"]), capi.iptr(rd)))
         self.rc = float(rc)
+        self.n_sites = [int(c.n_sites) for c in comps.components]
         self.has_rot = any(c.n_sites > 1 or len(c.dipoles) or len(c.quadrupoles) or
                            np.any(c.lj[:, :3] != 0) or np.any(c.charges[:, :3] != 0) for c in comps.components)
 
@@ -316,6 +319,46 @@ class DeviceEngine:
         if n.value:
             self._chk(self.lib.ls1hip_run_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
         return out
+
+    # -- radial distribution functions (ls1hip_rdf_*: the reference's RDF plugin + RDFCellProcessor) ---------------------------
+    def rdf_config(self, bins: int, interval_length: float, site_rdf: bool = True):
+        """bins = 0 switches the sampling off and frees the device histograms."""
+        self._chk(self.lib.ls1hip_rdf_config(self.ctx, int(bins), float(interval_length), int(bool(site_rdf))))
+        self.rdf_bins = int(bins)
+
+    def rdf_layout(self):
+        a = C.c_size_t(); b = C.c_size_t()
+        self._chk(self.lib.ls1hip_rdf_layout(self.ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def rdf_sample(self):
+        """One traversal over the current positions (molecules binned, halo valid), added to the device histograms."""
+        self._chk(self.lib.ls1hip_rdf_sample(self.ctx))
+
+    def rdf_read(self):
+        """LOCAL counts of this rank: mol uint64 [pairs, bins] (pairs (i, j >= i) in the order of RDF::collectRDF), site = list of
+        uint64 [n_i, n_j, bins] blocks of the pairs with n_i + n_j > 2 (their (i, j) in site_pairs; empty with site_rdf off),
+        n_per_component, samples."""
+        mw, sw = self.rdf_layout()
+        bins = self.rdf_bins
+        ns = self.n_sites
+        mol = np.zeros(mw, dtype=np.uint64); site = np.zeros(max(sw, 1), dtype=np.uint64)
+        npc = np.zeros(len(ns), dtype=np.uint64); smp = C.c_uint64()
+        self._chk(self.lib.ls1hip_rdf_read(self.ctx, mol.ctypes.data_as(capi._u64p), mw, site.ctypes.data_as(capi._u64p), sw,
+                                           npc.ctypes.data_as(capi._u64p), C.byref(smp)))
+        blocks, pairs, at = [], [], 0
+        if sw:
+            for i in range(len(ns)):
+                for j in range(i, len(ns)):
+                    if ns[i] + ns[j] > 2:
+                        n = ns[i] * ns[j] * bins
+                        blocks.append(site[at:at + n].reshape(ns[i], ns[j], bins))
+                        pairs.append((i, j))
+                        at += n
+        return dict(mol=mol.reshape(-1, bins), site=blocks, site_pairs=pairs, n_per_component=npc, samples=int(smp.value))
+
+    def rdf_reset(self):
+        self._chk(self.lib.ls1hip_rdf_reset(self.ctx))
 
     # -- multi-GPU plumbing -----------------------------------------------------------------------------------------
     def export_counts(self, kind: int):

@@ -38,6 +38,9 @@ class Domain:
     def getGlobalLength(self, d):
         return float(self._globalLength[d])
 
+    def getGlobalVolume(self):
+        return float(self._globalLength[0] * self._globalLength[1] * self._globalLength[2])
+
     def setLocalUpot(self, u):
         self._localUpot = float(u)
 
@@ -138,6 +141,215 @@ class VectorizedCellProcessor(CellProcessor):
         self._domain.setLocalUpot(self._upot)
 
 
+class RDFCellProcessor(CellProcessor):
+    """RDFCellProcessor(cutoffRadius, rdf) — adapter/RDFCellProcessor.h: the pair loops (RDFCellProcessor.cpp:18-133) are one
+    sampling pass on the device (LinkedCells.traverseCells)."""
+
+    def __init__(self, cutoffRadius: float, rdf: "RDF"):
+        super().__init__(cutoffRadius, cutoffRadius)
+        self._rdf = rdf
+
+    def initTraversal(self):
+        pass
+
+    def endTraversal(self):
+        pass
+
+
+def _g5(x) -> str:
+    """operator<< of a double at precision(5) (RDF.cpp:479): printf's %.5g; glibc writes a NaN with its sign"""
+    x = float(x)
+    if x != x:
+        return "-nan" if np.signbit(x) else "nan"
+    return "%.5g" % x
+
+
+def _div(a, b) -> float:
+    """IEEE division (the reference divides by counters that may be zero)"""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+class RDF:
+    """The reference's RDF plugin (io/RDF.h, io/RDF.cpp) over the device histograms: constructor arguments = the nodes
+    RDF::readXML reads (RDF.cpp:154-179); the numbers of sites come from the component set (RDF::init, RDF.cpp:35-151)."""
+
+    def __init__(self, components: ComponentSet, cutoffRadius: float, *, writefrequency: int = 1, samplingfrequency: int = 1,
+                 outputprefix: str = "mardyn", bins: int = 1, intervallength: float = 1.0, angularbins: int = 1,
+                 initStatistics: int = 0):
+        if angularbins > 1:
+            raise NotImplementedError("angular RDF (angularbins > 1) is not sampled on the device")
+        self._writeFrequency = int(writefrequency)
+        self._samplingFrequency = int(samplingfrequency)
+        self._outputPrefix = str(outputprefix)
+        self._bins = int(bins)
+        self._intervalLength = float(intervallength)
+        self._initStatistics = int(initStatistics)
+        self._numSites = [int(c.n_sites) for c in components.components]
+        self._numberOfComponents = nC = len(self._numSites)
+        self._doCollectSiteRDF = any(self._numSites[i] + self._numSites[j] > 2 for i in range(nC) for j in range(i, nC))
+        self._cellProcessor = RDFCellProcessor(cutoffRadius, self)
+        self._engine = None
+        self._accumulatedNumberOfRDFTimesteps = 0
+        self._globalAccumulatedCtr = np.zeros(nC, dtype=np.uint64)
+        self._globalAccumulatedDistribution = np.zeros((nC * (nC + 1) // 2, self._bins), dtype=np.uint64)
+        self._globalAccumulatedSiteDistribution = {p: np.zeros((self._numSites[p[0]], self._numSites[p[1]], self._bins), dtype=np.uint64)
+                                                   for p in self._site_pairs()}
+        self._zero_current()
+
+    # component pair (i, j >= i) -> row of the molecule histogram, in the order of RDF::collectRDF (RDF.cpp:235-241)
+    def _pair(self, i, j):
+        nC = self._numberOfComponents
+        return i * nC - (i * (i - 1)) // 2 + (j - i)
+
+    def _site_pairs(self):
+        nC, ns = self._numberOfComponents, self._numSites
+        return [(i, j) for i in range(nC) for j in range(i, nC) if ns[i] + ns[j] > 2] if self._doCollectSiteRDF else []
+
+    def _zero_current(self):
+        nC = self._numberOfComponents
+        self._numberOfRDFTimesteps = 0
+        self._globalCtr = np.zeros(nC, dtype=np.uint64)
+        self._distribution_global = np.zeros((nC * (nC + 1) // 2, self._bins), dtype=np.uint64)
+        self._siteDistribution_global = {p: np.zeros((self._numSites[p[0]], self._numSites[p[1]], self._bins), dtype=np.uint64)
+                                         for p in self._site_pairs()}
+
+    def _configure(self, engine: DeviceEngine):
+        if self._engine is not engine:
+            engine.rdf_config(self._bins, self._intervalLength, self._doCollectSiteRDF)
+            self._engine = engine
+
+    def isEnabledSiteRDF(self):
+        return self._doCollectSiteRDF
+
+    # --- RDF::afterForces, RDF.cpp:573-581 (tickRDF and accumulateNumberOfMolecules are part of the device pass)
+    def afterForces(self, particleContainer, domainDecomp, simstep: int):
+        if simstep % self._samplingFrequency == 0 and simstep > self._initStatistics:
+            self._numberOfRDFTimesteps += 1
+            particleContainer.traverseCells(self._cellProcessor)
+
+    # --- RDF::collectRDF, RDF.cpp:231-306: local counts of the device -> global values (summed over the ranks by a decomposition
+    # that offers rdf_collect, decomp.py)
+    def collectRDF(self, domainDecomp=None):
+        if self._engine is None:
+            return
+        collect = getattr(domainDecomp, "rdf_collect", None)
+        self.setGlobal(collect(self._engine) if collect else self._engine.rdf_read())
+
+    def setGlobal(self, counts):
+        """Global values of the current interval from a dict as DeviceEngine.rdf_read / decomp.rdf_collect return it."""
+        self._numberOfRDFTimesteps = int(counts["samples"])
+        self._globalCtr = np.asarray(counts["n_per_component"], dtype=np.uint64).copy()
+        self._distribution_global = np.asarray(counts["mol"], dtype=np.uint64).reshape(-1, self._bins).copy()
+        self._siteDistribution_global = {p: np.asarray(b, dtype=np.uint64).copy() for p, b in zip(self._site_pairs(), counts["site"])}
+
+    # --- RDF::accumulateRDF, RDF.cpp:202-229
+    def accumulateRDF(self):
+        if self._numberOfRDFTimesteps <= 0:
+            return
+        self._accumulatedNumberOfRDFTimesteps += self._numberOfRDFTimesteps
+        self._globalAccumulatedCtr += self._globalCtr
+        self._globalAccumulatedDistribution += self._distribution_global
+        for p, b in self._siteDistribution_global.items():
+            self._globalAccumulatedSiteDistribution[p] += b
+
+    # --- RDF::reset, RDF.cpp:309-340: everything but the accumulated values
+    def reset(self):
+        self._zero_current()
+        if self._engine is not None:
+            self._engine.rdf_reset()
+
+    # --- RDF::endStep, RDF.cpp:343-375
+    def endStep(self, particleContainer, domainDecomp, domain: Domain, simStep: int, directory: str = "."):
+        import os
+
+        if self._numberOfRDFTimesteps <= 0:
+            return
+        if simStep > 0 and simStep % self._writeFrequency == 0:
+            self.collectRDF(domainDecomp)
+            rank = domainDecomp.getRank() if hasattr(domainDecomp, "getRank") else 0
+            if rank == 0:
+                self.accumulateRDF()
+                for i in range(self._numberOfComponents):
+                    for j in range(i, self._numberOfComponents):
+                        self.writeToFile(domain, os.path.join(directory, "%s_%d-%d.%09d.rdf" % (self._outputPrefix, i, j, simStep)), i, j)
+            self.reset()
+
+    # --- RDF::writeToFile, RDF.cpp:457-571
+    def writeToFile(self, domain: Domain, filename: str, i: int, j: int):
+        ni, nj = self._numSites[i], self._numSites[j]
+        sites = ni + nj > 2
+        V = domain.getGlobalVolume()
+        nT, nA = self._numberOfRDFTimesteps, self._accumulatedNumberOfRDFTimesteps
+        N_i = _div(int(self._globalCtr[i]), nT)
+        N_Ai = _div(int(self._globalAccumulatedCtr[i]), nA)
+        N_j = _div(int(self._globalCtr[j]), nT)
+        N_Aj = _div(int(self._globalAccumulatedCtr[j]), nA)
+        rho_i, rho_Ai, rho_j, rho_Aj = N_i / V, N_Ai / V, N_j / V, N_Aj / V
+        out = ["# r\tcurr.{loc, int}\taccu.{loc, int}\t\tdV\tNpair(curr.)\tNpair(accu.)\t\tnorm(curr.)\tnorm(accu.)"]
+        if sites:
+            for m in range(ni):
+                out.append("\t")
+                for n in range(nj):
+                    out.append("\t(%d, %d)_curr{loc, int}   (%d, %d)_accu{loc, int}" % (m, n, m, n))
+        out.append("\n")
+        out.append("# \n# ctr_i: %d\n# ctr_j: %d\n# V: %s\n# _universalRDFTimesteps: %d\n# _universalAccumulatedTimesteps: %d"
+                   "\n# _samplingFrequency: %d\n# rho_i: %s (acc. %s)\n# rho_j: %s (acc. %s)\n# \n"
+                   % (int(self._globalCtr[i]), int(self._globalCtr[j]), _g5(V), nT, nA, self._samplingFrequency, _g5(rho_i), _g5(rho_Ai),
+                      _g5(rho_j), _g5(rho_Aj)))
+        out.append("#r\trdf\trdf_{integral}\tacc_rdf acc_rdf_{integral}\t\tdV\tNpair(curr.)\tNpair(accu.)\t\tnormalization(curr.)\tnormalization(accu.)")
+        if sites:
+            for m in range(ni):
+                out.append("\t")
+                for n in range(nj):
+                    out.append("\t(%d,%d)_curr{rdf, rdf_integral}   (%d,%d)_accu{rdf, rdf_integral}" % (m, n, m, n))
+        out.append("\n")
+        p = self._pair(i, j)
+        dist, adist = self._distribution_global[p], self._globalAccumulatedDistribution[p]
+        sdist = self._siteDistribution_global.get((i, j)) if sites else None
+        sadist = self._globalAccumulatedSiteDistribution.get((i, j)) if sites else None
+        Nsite_pair_int = np.zeros((ni, nj))
+        Nsite_Apair_int = np.zeros((ni, nj))
+        N_pair_int = N_Apair_int = 0.0
+        w = self._intervalLength
+        for l in range(self._bins):
+            rmin, rmid, rmax = l * w, (l + 0.5) * w, (l + 1.0) * w
+            r3min, r3max = rmin * rmin * rmin, rmax * rmax * rmax
+            dV = (4.0 / 3.0) * np.pi * (r3max - r3min)
+            N_pair = _div(int(dist[l]), nT)
+            N_pair_int += N_pair
+            N_Apair = _div(int(adist[l]), nA)
+            N_Apair_int += N_Apair
+            if i == j:
+                N_pair_norm = 0.5 * N_i * (N_i - 1.0) * dV / V
+                N_Apair_norm = 0.5 * N_Ai * (N_Ai - 1.0) * dV / V
+                N_pair_int_norm = 0.5 * N_i * (N_i - 1.0) * 4.1887902 * r3max / V
+                N_Apair_int_norm = 0.5 * N_Ai * (N_Ai - 1.0) * 4.1887902 * r3max / V
+            else:
+                N_pair_norm = N_i * N_j * dV / V
+                N_Apair_norm = N_Ai * N_Aj * dV / V
+                N_pair_int_norm = N_i * N_j * 4.1887902 * r3max / V
+                N_Apair_int_norm = N_Ai * N_Aj * 4.1887902 * r3max / V
+            out.append("%s\t%s %s\t%s %s\t\t%s\t%s\t%s\t\t%s\t%s" % (
+                _g5(rmid), _g5(_div(N_pair, N_pair_norm)), _g5(_div(N_pair_int, N_pair_int_norm)), _g5(_div(N_Apair, N_Apair_norm)),
+                _g5(_div(N_Apair_int, N_Apair_int_norm)), _g5(dV), _g5(N_pair), _g5(N_Apair), _g5(N_pair_norm), _g5(N_Apair_norm)))
+            if sites:
+                for m in range(ni):
+                    out.append("\t")
+                    for n in range(nj):
+                        # the writer's factor 1/2 for the double count of same-component pairs with m != n (RDF.cpp:556-558)
+                        cf = 0.5 if (i == j and m != n) else 1.0
+                        ps = _div(cf * int(sdist[m, n, l]), nT)
+                        Nsite_pair_int[m, n] += ps
+                        ap = _div(cf * int(sadist[m, n, l]), nA)
+                        Nsite_Apair_int[m, n] += ap
+                        out.append("\t%s %s   %s %s" % (_g5(_div(ps, N_pair_norm)), _g5(_div(Nsite_pair_int[m, n], N_pair_int_norm)),
+                                                        _g5(_div(ap, N_Apair_norm)), _g5(_div(Nsite_Apair_int[m, n], N_Apair_int_norm))))
+            out.append("\n")
+        with open(filename, "w") as f:
+            f.write("".join(out))
+
+
 class LinkedCells:
     """Device-resident replacement of the reference's LinkedCells (seam B of SURVEY.md 8b).
 
@@ -170,7 +382,14 @@ class LinkedCells:
         pass
 
     # --- LinkedCells::traverseCells, LinkedCells.cpp:564-575
-    def traverseCells(self, cellProcessor: VectorizedCellProcessor):
+    def traverseCells(self, cellProcessor: CellProcessor):
+        if isinstance(cellProcessor, RDFCellProcessor):
+            # the RDF traversal: one sampling pass over the same cells (histograms stay on the device until RDF::collectRDF)
+            cellProcessor.initTraversal()
+            cellProcessor._rdf._configure(self.engine)
+            self.engine.rdf_sample()
+            cellProcessor.endTraversal()
+            return
         cellProcessor.initTraversal()
         cellProcessor._accumulate(*self.engine.forces(0))
         cellProcessor.endTraversal()
