@@ -449,7 +449,9 @@ static int alloc_mol(ls1hip_ctx* c, size_t n) {
 	// the smallest brick is 8 cells (1x4x2 or 2x2x2), rounded up per dimension, + 16 for the XCD-aligned grid.  (Sized by
 	// molecules only, small / sparse boxes silently fell back to the generic kernel: found by the random-box sweep.)
 	const size_t max_bricks = (size_t)c->g.box[0] * ((c->g.box[1] + 1) / 2) * ((c->g.box[2] + 1) / 2) + 16;
-	const size_t partials_cap = std::max(cap_real / 32 + 16, max_bricks);  // generic kernel: up to 4 lanes per molecule, 128 threads
+	size_t partials_cap = std::max(cap_real / 32 + 16, max_bricks);  // generic kernel: up to 4 lanes per molecule, 128 threads
+	// list force pass: one row per wave of every workgroup (grid = bricks rounded up to a multiple of 8)
+	if (c->vl_on) partials_cap = std::max(partials_cap, ((size_t)verlet_brick_count(c->g) + 8) * (size_t)verlet_partial_rows());
 	if (cap_real <= c->cap_real && cap_halo <= c->cap_halo && partials_cap <= c->partials_cap) return 0;
 	free_mol(c);
 	const size_t tot = cap_real + cap_halo;

@@ -285,6 +285,7 @@ static int launch_forces(ls1hip_ctx* c, const ForcePass& fp) {
 	rm.kin_in_slot1 = (fuse || fp.post_kick) && c->one_clj;  // (multi-site list passes: their own partial buffers, see above)
 	rm.target_T = (fp.post_kick && c->thermostat_on && c->one_clj) ? c->thermostat_T : 0.;
 	rm.log = c->log_row;
+	if (fp.vl && c->one_clj) rm.rows = verlet_partial_rows();  // (launch_force_verlet succeeded or the pass failed above)
 	if (fp.vl && fuse && c->one_clj) {
 		rm.vmax_in_slot2 = true;
 		rm.last_pass = which != 1;
@@ -677,7 +678,7 @@ static int ensure_verlet_buffers(ls1hip_ctx* c) {
 		int rc;
 		if ((rc = dalloc(c, &c->d_vl_words, words)) || (rc = dalloc(c, &c->d_vl_nw, tiles)) ||
 			(rc = dalloc(c, &c->d_vl_rec, (size_t)nbricks * verlet_record_words())) || (rc = dalloc(c, &c->d_vl_ii, tiles * 64)) ||
-			(rc = dalloc(c, &c->d_vl_gi, tiles * 64)) || (rc = dalloc(c, &c->d_vl_top2, (size_t)nbricks * 2)) ||
+			(rc = dalloc(c, &c->d_vl_gi, tiles * 64)) || (rc = dalloc(c, &c->d_vl_top2, verlet_top2_doubles(nbricks))) ||
 			(rc = dalloc(c, &c->d_vl_acc, (size_t)nbricks)))
 			return rc;
 		c->vl_words_cap = words;

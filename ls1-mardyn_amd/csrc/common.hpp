@@ -101,7 +101,7 @@ struct ForceParams {
 	double *Fx, *Fy, *Fz, *Mx, *My, *Mz, *Vix, *Viy, *Viz;
 	const CompTable* ct;
 	DevCounters* cnt;
-	double* partials;  // [gridDim][4]
+	double* partials;  // [gridDim][4]; the list force pass (kernels_force_verlet.hip): [gridDim][waves][4]
 	uint32_t n_real_cap;  // launch bound (n_real is read from cnt for device-driven loops)
 	int which;         // 0 all, 1 inner cells, 2 boundary cells, 3 all non-halo cells (seam A)
 	uint32_t n_fixed;  // if != 0: number of molecules (overrides cnt->n_real; seam A)
@@ -141,7 +141,7 @@ struct ForceParams {
 	uint32_t* vl_rec;    // [brick][verlet_record_words()]: region cell table + flags, written by the build
 	uint16_t* vl_ii;     // [brick][tiles * 64]: LDS slot of every owned molecule
 	uint32_t* vl_gi;     // [brick][tiles * 64]: global index of every owned molecule
-	double* vl_top2;     // [brick][2] or nullptr: the two largest |v_drift|^2 of the brick's owned molecules (local rebuild criterion)
+	double* vl_top2;     // [brick][waves][2] or nullptr: per wave, the two largest |v_drift|^2 of its owned molecules (local rebuild criterion)
 };
 
 // inner / boundary brick lists of the LJ brick kernels for the current grid and brick shape (kernels_force_lj.hip)
@@ -258,7 +258,7 @@ struct ls1hip_ctx {
 	uint32_t* d_vl_rec = nullptr;
 	uint16_t* d_vl_ii = nullptr;
 	uint32_t* d_vl_gi = nullptr;
-	double* d_vl_top2 = nullptr;  // [brick][2] two largest |v_drift|^2 per brick (local rebuild criterion)
+	double* d_vl_top2 = nullptr;  // [brick][waves][2] two largest |v_drift|^2 per wave, then [brick][2] folded (local rebuild criterion)
 	double* d_vl_acc = nullptr;   // [brick] accumulated pair-displacement bound of the brick's neighbourhood
 	long opt_local_rebuild = 1;   // single periodic domain, fused FP64 list passes: rebuild by the local criterion
 	size_t vl_words_cap = 0, vl_tiles_cap = 0;
@@ -418,9 +418,12 @@ void verlet_brick_shape(int shape[3]);
 int verlet_record_words();
 // speed_factor: the speeds in top2 are multiplied by it (1: they are drift speeds; max(beta, 1) for the bounds a post-kick pass left;
 // < 0: max(cnt->beta[0], 1) read on the device)
-void launch_bound_local(const Grid& g, const double* top2, double* acc, DevCounters* cnt, double dt, double limit, hipStream_t s,
+// top2: the force pass's per-wave rows [brick][rows][2], folded per brick into [brick][2] behind them (verlet_top2_doubles in all)
+void launch_bound_local(const Grid& g, double* top2, double* acc, DevCounters* cnt, double dt, double limit, hipStream_t s,
 						double speed_factor = 1.);
 long verlet_brick_count(const Grid& g);  // cells per brick edge of the list kernels
+int verlet_partial_rows();               // rows of partials (and of vl_top2) a workgroup of the list force pass stores: one per wave
+size_t verlet_top2_doubles(long nbricks);
 // brick-tiled multi-site kernel (kernels_force_ms.hip); returns false if it cannot handle the configuration
 bool launch_force_ms(const ForceParams& p, bool with_vi, bool has_rot, bool one_component, hipStream_t s, uint32_t* nblocks,
 					 size_t partials_cap, double mean_per_cell, BrickLists* bl);
@@ -447,6 +450,7 @@ struct ReduceMode {
 	bool kin_in_slot1 = false;  // slot 1 = sum m v^2 of a fused pass
 	double target_T = 0.;       // ... and, if > 0, the thermostat factors are derived from it (Domain.cpp:225-240)
 	double* log = nullptr;      // step-log row to refresh
+	int rows = 1;               // rows of partials per workgroup, folded in the order 0 .. rows - 1 (list force pass: one per wave)
 	// list-reuse mode: slot 2 = max |v_drift|^2 (combined by max).  On the LAST pass of a step the displacement bound is
 	// advanced by dt * sqrt(vmax2) (after being reset when the lists were rebuilt in this step) and the rebuild flag
 	// {seq, bound > limit} is published to the host-visible word `flag`.

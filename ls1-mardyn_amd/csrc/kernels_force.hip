@@ -282,13 +282,23 @@ void launch_clear_macro(DevCounters* cnt, hipStream_t s) { hipLaunchKernelGGL(k_
 // deterministic reduction of the per-workgroup partials in two fixed-shape stages (RED_BLOCKS x 256 threads, then one
 // block), ADDED to cnt->macro; the summation order depends only on the number of partials, never on timing.
 constexpr int RED_BLOCKS = 128;
-__global__ void __launch_bounds__(256) k_force_reduce1(const double* partials, uint32_t nblocks, double* stage, int max2) {
+// rows > 1 (list force pass: one row per wave): the rows of a workgroup are folded first, from zero and in the order 0 .. rows - 1 —
+// the workgroup's own serial fold of earlier versions, bit for bit — and the fold enters the sums like a single row
+__global__ void __launch_bounds__(256) k_force_reduce1(const double* partials, uint32_t nblocks, double* stage, int max2, int rows) {
 	double v[4] = {0., 0., 0., 0.};
-	for (uint32_t b = blockIdx.x * 256 + threadIdx.x; b < nblocks; b += RED_BLOCKS * 256)
-		for (int k = 0; k < 4; ++k) {
-			const double x = partials[(size_t)b * 4 + k];
-			v[k] = (k == 2 && max2) ? fmax(v[k], x) : v[k] + x;
+	for (uint32_t b = blockIdx.x * 256 + threadIdx.x; b < nblocks; b += RED_BLOCKS * 256) {
+		const double* const p = partials + (size_t)b * rows * 4;
+		double x[4] = {p[0], p[1], p[2], p[3]};
+		if (rows > 1) {
+			for (int k = 0; k < 4; ++k) x[k] = (k == 2 && max2) ? fmax(0., x[k]) : 0. + x[k];
+			for (int r = 1; r < rows; ++r)
+				for (int k = 0; k < 4; ++k) {
+					const double y = p[r * 4 + k];
+					x[k] = (k == 2 && max2) ? fmax(x[k], y) : x[k] + y;
+				}
 		}
+		for (int k = 0; k < 4; ++k) v[k] = (k == 2 && max2) ? fmax(v[k], x[k]) : v[k] + x[k];
+	}
 	__shared__ double red[4][4];
 	for (int k = 0; k < 4; ++k) v[k] = (k == 2 && max2) ? wave_max(v[k]) : wave_sum(v[k]);
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -385,7 +395,7 @@ void launch_force_reduce(DevCounters* cnt, const double* partials, uint32_t nblo
 	a.overwrite = m.overwrite; a.kin_in_slot1 = m.kin_in_slot1; a.vmax_in_slot2 = m.vmax_in_slot2; a.last_pass = m.last_pass;
 	a.lists_rebuilt = m.lists_rebuilt; a.local_criterion = m.local_criterion; a.dt = m.dt; a.limit = m.limit; a.seq = m.seq; a.flag = m.flag; a.log = m.log;
 	a.target_T = m.target_T;
-	hipLaunchKernelGGL(k_force_reduce1, dim3(RED_BLOCKS), dim3(256), 0, s, partials, nblocks, stage, m.vmax_in_slot2 ? 1 : 0);
+	hipLaunchKernelGGL(k_force_reduce1, dim3(RED_BLOCKS), dim3(256), 0, s, partials, nblocks, stage, m.vmax_in_slot2 ? 1 : 0, m.rows);
 	hipLaunchKernelGGL(k_force_reduce2, dim3(1), dim3(RED_BLOCKS), 0, s, cnt, stage, a);
 }
 

@@ -37,6 +37,7 @@
 // the FP64 pair body.
 #include "common.hpp"
 #include "brick.hpp"
+#include "dma_run.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -498,8 +499,12 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 	}
 }
 
-// workgroup reduction of the totals -> one row of partials {U/2-weighted u6, sum m v^2, max |v_drift|^2, virial}
-__device__ __forceinline__ void store_partials(const ForceParams& P, const Totals& tot, double (*red)[4], int brick_id = -1) {
+// Totals of a workgroup -> VNW rows of partials {U/2-weighted u6, sum m v^2, max |v_drift|^2, virial}, one per WAVE: lane 0 of every
+// wave stores its own row (and the wave's two largest |v_drift|^2) as soon as the wave is through its molecules — no barrier behind
+// the pair loop, no serial pass of thread 0 over the waves while the workgroup's LDS and registers stay allotted.  The consumers
+// (k_force_reduce1 with rows = VNW; k_top2_fold) fold the rows of a workgroup in the fixed order 0 .. VNW - 1, the order thread 0
+// used to fold them in: the sums keep their bits.
+__device__ __forceinline__ void store_partials(const ForceParams& P, const Totals& tot, int brick_id = -1) {
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	// every ordered pair contributes half of the pair's U and virial (see kernels_force.hip); the two largest |v_drift|^2 of the
 	// wave (local rebuild criterion) are reduced in the same steps — as an extra loop behind the sums their six dependent
@@ -513,37 +518,23 @@ __device__ __forceinline__ void store_partials(const ForceParams& P, const Total
 		b = fmax(fmin(a, a2), fmax(b, b2));
 		a = fmax(a, a2);
 	}
-	const double vm = a;
-	const bool top2 = P.vl_top2 != nullptr && brick_id >= 0;
-	__shared__ double red2[VNW];
-	if (lane == 0) red2[wv] = b;
 	if (lane == 0) {
-		red[wv][0] = u;
-		red[wv][1] = kn;
-		red[wv][2] = vm;
-		red[wv][3] = v;
-	}
-	__syncthreads();
-	if (tid == 0) {
-		double* out = P.partials + (size_t)blockIdx.x * 4;
-		double su = 0., sk = 0., sm = 0., sv = 0., sb = 0.;
-		for (int i = 0; i < VNW; ++i) {
-			su += red[i][0];
-			sk += red[i][1];
-			if (top2) sb = fmax(fmin(sm, red[i][2]), fmax(sb, red2[i]));
-			sm = fmax(sm, red[i][2]);
-			sv += red[i][3];
-		}
-		out[0] = su;
-		out[1] = sk;  // fused mode: sum m v^2 (see k_force_lj_brick)
-		out[2] = P.fuse == 2 ? 0. : sm;  // fused mode: max |v_drift|^2 of the molecules (combined by max in the reduction); a
-		                                 // post-kick pass only feeds vl_top2 (slot 2 is a SUM there: the reaction-field term)
-		out[3] = sv;
-		if (top2) {
-			P.vl_top2[2 * (size_t)brick_id] = sm;
-			P.vl_top2[2 * (size_t)brick_id + 1] = sb;
+		double* out = P.partials + ((size_t)blockIdx.x * VNW + (size_t)wv) * 4;
+		out[0] = u;
+		out[1] = kn;  // fused mode: sum m v^2 (see k_force_lj_brick)
+		out[2] = P.fuse == 2 ? 0. : a;  // fused mode: max |v_drift|^2 of the molecules (combined by max in the reduction); a
+		                                // post-kick pass only feeds vl_top2 (slot 2 is a SUM there: the reaction-field term)
+		out[3] = v;
+		if (P.vl_top2 != nullptr && brick_id >= 0) {
+			double* const t2 = P.vl_top2 + ((size_t)brick_id * VNW + (size_t)wv) * 2;
+			t2[0] = a;
+			t2[1] = b;
 		}
 	}
+}
+// a workgroup without a brick: VNW rows of zeros
+__device__ __forceinline__ void store_zero_partials(const ForceParams& P) {
+	if (threadIdx.x < VNW * 4) P.partials[(size_t)blockIdx.x * (VNW * 4) + threadIdx.x] = 0.;
 }
 
 // region table + brick prefix of one brick, by the whole workgroup (one-brick-per-workgroup kernels)
@@ -645,35 +636,49 @@ __device__ __forceinline__ void stage_positions(const ForceParams& P, const Bric
 	}
 }
 
-// LDS-DMA form of the staging for REGULAR bricks (gfx950 global_load_lds_dword: per-lane global source, wave-uniform LDS base +
-// lane * 4, no VGPR destination, no ds_write): the region image in LDS is, row by row, exactly the global layout — a region row
-// of six x-neighbour cells is one contiguous run of molecules in the cell-sorted arrays (several runs where halo cells, which live
-// in their own segment, interrupt it) — so every run is copied dword-wise by one wave: three rows per wave, descriptors through
-// scalar loads of the build's record.  8-byte alignment of both sides is enough for the dword form (the 16-byte form would need
-// runs padded to even molecule counts on both sides, i.e. another list-entry encoding).  tools/probes/glds_probe.hip checks the
-// semantics the copy relies on (EXEC-masked lanes write nothing, unaligned-to-16 runs land bit-exactly).
+// LDS-DMA form of the staging for REGULAR bricks (gfx950 global_load_lds: per-lane global source, wave-uniform LDS base + lane *
+// size, no VGPR destination, no ds_write): the region image in LDS is, row by row, exactly the global layout — a region row of six
+// x-neighbour cells is one contiguous run of molecules in the cell-sorted arrays (several runs where halo cells, which live in
+// their own segment, interrupt it) — so every run is copied by one wave: three rows per wave, descriptors through scalar loads of
+// the build's record.
+// A run is split by dma_run_split (dma_run.hpp): the LDS side of the 16-byte form (two molecules per lane: 1 KiB per wave
+// instruction instead of 256 B) must start on an even slot, so an odd first slot goes dword-wise (two lanes), the body with the
+// 16-byte form (last instruction EXEC-masked), an odd last molecule dword-wise again; the global side of the 16-byte form is per
+// lane and starts on any molecule (8-byte aligned).  Slot numbers stay the plain prefix sum of the cell counts — the list entries'
+// encoding — and every instruction writes slots of its own run only.  tools/probes/glds_probe.hip checks the semantics the copy
+// relies on (EXEC-masked lanes write nothing, both forms land bit-exactly from sources of either parity, the data is visible to
+// OTHER waves behind vmcnt(0) + barrier).
 typedef __attribute__((address_space(3))) void* ls1_lds_ptr;
 typedef const __attribute__((address_space(1))) void* ls1_glb_ptr;
 __device__ __forceinline__ void stage_positions_dma(const ForceParams& P, const uint32_t* __restrict__ rec, double* sx, double* sy, double* sz,
 													uint32_t total) {
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-	auto copy_run = [&](uint32_t s0, uint32_t g0, uint32_t n) {  // n molecules from global index g0 to LDS slot s0 (all wave-uniform)
-		const uint32_t nd = 2u * n;
-		const uint32_t* const gx = reinterpret_cast<const uint32_t*>(P.x + g0);
-		const uint32_t* const gy = reinterpret_cast<const uint32_t*>(P.y + g0);
-		const uint32_t* const gz = reinterpret_cast<const uint32_t*>(P.z + g0);
-		uint32_t* const lx = reinterpret_cast<uint32_t*>(sx + VPS * s0);
-		uint32_t* const ly = reinterpret_cast<uint32_t*>(sy + VPS * s0);
-		uint32_t* const lz = reinterpret_cast<uint32_t*>(sz + VPS * s0);
-		for (uint32_t k0 = 0; k0 < nd; k0 += 64u) {
-			const uint32_t d = k0 + (uint32_t)lane;
-			if (d < nd) {
-				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gx + d), (ls1_lds_ptr)(lx + k0), 4, 0, 0);
-				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gy + d), (ls1_lds_ptr)(ly + k0), 4, 0, 0);
-				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gz + d), (ls1_lds_ptr)(lz + k0), 4, 0, 0);
+	// one molecule (two dwords) by lanes 0 and 1
+	auto copy_one = [&](const double* gx, const double* gy, const double* gz, double* lx, double* ly, double* lz) {
+		if (lane < 2) {
+			__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(reinterpret_cast<const uint32_t*>(gx) + lane), (ls1_lds_ptr)lx, 4, 0, 0);
+			__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(reinterpret_cast<const uint32_t*>(gy) + lane), (ls1_lds_ptr)ly, 4, 0, 0);
+			__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(reinterpret_cast<const uint32_t*>(gz) + lane), (ls1_lds_ptr)lz, 4, 0, 0);
+		}
+	};
+	auto copy_run = [&](uint32_t s0, uint32_t g0, uint32_t n) {  // n >= 1 molecules from global index g0 to LDS slot s0 (all wave-uniform)
+		const DmaRunSplit sp = dma_run_split(s0, n);
+		const double *gx = P.x + g0, *gy = P.y + g0, *gz = P.z + g0;
+		double *lx = sx + s0, *ly = sy + s0, *lz = sz + s0;  // (sx is 16-byte aligned and VCO is even: sy and sz share the parity of sx)
+		if (sp.head) copy_one(gx, gy, gz, lx, ly, lz);
+		gx += sp.head; gy += sp.head; gz += sp.head;
+		lx += sp.head; ly += sp.head; lz += sp.head;
+		for (uint32_t k0 = 0; k0 < sp.pairs; k0 += 64u) {
+			const uint32_t q = k0 + (uint32_t)lane;
+			if (q < sp.pairs) {
+				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gx + 2u * q), (ls1_lds_ptr)(lx + 2u * k0), 16, 0, 0);
+				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gy + 2u * q), (ls1_lds_ptr)(ly + 2u * k0), 16, 0, 0);
+				__builtin_amdgcn_global_load_lds((ls1_glb_ptr)(gz + 2u * q), (ls1_lds_ptr)(lz + 2u * k0), 16, 0, 0);
 			}
 		}
+		const uint32_t t = 2u * sp.pairs;
+		if (sp.tail) copy_one(gx + t, gy + t, gz + t, lx + t, ly + t, lz + t);
 	};
 	static_assert(VPS == 1, "the DMA staging copies the separate x / y / z arrays");
 	for (int r = wv; r < VRY * VRZ; r += VNW) {
@@ -698,6 +703,9 @@ __device__ __forceinline__ void stage_positions_dma(const ForceParams& P, const 
 		sy[VPS * (total + tid)] = VFAR;
 		sz[VPS * (total + tid)] = VFAR;
 	}
+	// The data of a DMA is an LDS write pending on vmcnt: it must have landed before the staging barrier lets OTHER waves read it.
+	// (The compiler puts the same wait in front of __syncthreads() today; the copy does not depend on that choice.)
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // ---- BUILD ------------------------------------------------------------------------------------------------------------
@@ -941,7 +949,8 @@ __global__ void __launch_bounds__(VNT, 4) k_lj_verlet_build(ForceParams P, int n
 template <bool SHIFT, bool SIG1, bool FAST>
 __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int nbx, int nby, int nbz, int vgrid) {
 	constexpr int CAPS = VCAPS;
-	__shared__ double spos[3 * CAPS];
+	__shared__ __attribute__((aligned(16))) double spos[3 * CAPS];  // (16-byte DMA destinations: stage_positions_dma)
+	static_assert(VCO % 2 == 0, "sy and sz must be 16-byte aligned like sx");
 	double* const sx = spos;
 	double* const sy = spos + VCO;
 	double* const sz = spos + 2 * VCO;
@@ -949,7 +958,6 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int n
 	__shared__ uint32_t gbeg[VNRC];
 	__shared__ uint32_t bstart[VNBC + 1];
 	__shared__ uint32_t wsum[VNW];
-	__shared__ double red[VNW][4];
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	// FAST HEAD (the production launch: every brick, blocked order, per-brick data stored in launch order — did_mode 1): the
 	// workgroup's data index is pure arithmetic on blockIdx.x; the brick's identity (one dependent scalar load) and its grid
@@ -970,7 +978,7 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int n
 		did = bs.did;
 	}
 	if (!live) {  // uniform per workgroup
-		if (tid < 4) P.partials[(size_t)blockIdx.x * 4 + tid] = 0.;
+		store_zero_partials(P);
 		return;
 	}
 	LS1_HOOK_STAGGER();  // (nothing; timing variants)
@@ -1007,7 +1015,7 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int n
 		// loads, no scans, no table search; the only barrier of the workgroup is the one behind the staging
 		const BrickTab T = {cstart, gbeg, bstart};  // (only the two totals are read on this path)
 		brick_forces<SHIFT, SIG1>(P, T, sx, sy, sz, did, true, head, tot, rec_total, rec_ni, f_ii, f_gi, ii0, gi0);
-		store_partials(P, tot, red, fast_head ? (int)P.brick_list[slot] : bs.id);
+		store_partials(P, tot, fast_head ? (int)P.brick_list[slot] : bs.id);
 	} else {
 		if constexpr (fast_head) bs = brick_select_v<1, VBX, VBY, VBZ>(P, nbx, nby, nbz, (int)blockIdx.x, vgrid);
 		const BrickTab T = {cstart, gbeg, bstart};
@@ -1016,7 +1024,7 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int n
 		if (staged) stage_positions(P, T, sx, sy, sz, TotalOf{cstart[VNRC]});
 		__syncthreads();
 		brick_forces<SHIFT, SIG1>(P, T, sx, sy, sz, did, staged, head, tot, cstart[VNRC], bstart[VNBC]);
-		store_partials(P, tot, red, bs.id);
+		store_partials(P, tot, bs.id);
 	}
 }
 
@@ -1058,11 +1066,10 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet_sp(ForceParams P, in
 	float* const fx = fpos;
 	float* const fy = fpos + VCO;
 	float* const fz = fpos + 2 * VCO;
-	__shared__ double red[VNW][4];
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const BrickSel bs = brick_select<1, VBX, VBY, VBZ>(P, nbx, nby, nbz);
 	if (!bs.live) {  // uniform per workgroup
-		if (tid < 4) P.partials[(size_t)blockIdx.x * 4 + tid] = 0.;
+		store_zero_partials(P);
 		return;
 	}
 	const ListHead head = load_list_head(P, bs.did, wv, lane);
@@ -1257,7 +1264,7 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet_sp(ForceParams P, in
 			tot.vir += eps24 * dvir;
 		}
 	}
-	store_partials(P, tot, red, bs.id);
+	store_partials(P, tot, bs.id);
 }
 
 // ---- LOCAL REBUILD CRITERION ------------------------------------------------------------------------------------------------
@@ -1295,15 +1302,35 @@ __global__ void __launch_bounds__(256) k_bound_local(int nbx, int nby, int nbz, 
 	acc[b] = v;
 	if (v + cnt->vl_base > limit) atomicOr(&cnt->vl_local_excess, 1u);
 }
+// The force pass leaves the two largest |v_drift|^2 per WAVE (store_partials): rows [brick][VNW][2].  Folded here, once per brick and
+// coalesced, in the wave order 0 .. VNW - 1 (k_bound_local reads every brick 27 times), into [brick][2] behind the rows.
+__global__ void __launch_bounds__(256) k_top2_fold(long nb, const double* __restrict__ rows, double* __restrict__ top2) {
+	const long b = (long)blockIdx.x * 256 + threadIdx.x;
+	if (b >= nb) return;
+	const double2* const r = reinterpret_cast<const double2*>(rows) + (size_t)b * VNW;
+	double sm = 0., sb = 0.;
+#pragma unroll
+	for (int i = 0; i < VNW; ++i) {
+		const double2 t = r[i];
+		sb = fmax(fmin(sm, t.x), fmax(sb, t.y));
+		sm = fmax(sm, t.x);
+	}
+	top2[2 * (size_t)b] = sm;
+	top2[2 * (size_t)b + 1] = sb;
+}
 long verlet_brick_count(const Grid& g) {
 	return (long)((g.box[0] + VBX - 1) / VBX) * ((g.box[1] + VBY - 1) / VBY) * ((g.box[2] + VBZ - 1) / VBZ);
 }
-void launch_bound_local(const Grid& g, const double* top2, double* acc, DevCounters* cnt, double dt, double limit, hipStream_t s,
+int verlet_partial_rows() { return VNW; }
+size_t verlet_top2_doubles(long nbricks) { return (size_t)nbricks * (VNW + 1) * 2; }
+void launch_bound_local(const Grid& g, double* top2, double* acc, DevCounters* cnt, double dt, double limit, hipStream_t s,
 						double speed_factor) {
 	const int nbx = (g.box[0] + VBX - 1) / VBX, nby = (g.box[1] + VBY - 1) / VBY, nbz = (g.box[2] + VBZ - 1) / VBZ;
 	const long nb = (long)nbx * nby * nbz;
 	if (nb <= 0) return;
-	hipLaunchKernelGGL(k_bound_local, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, nbx, nby, nbz, top2, acc, cnt, dt, limit, speed_factor);
+	double* const folded = top2 + (size_t)nb * VNW * 2;
+	hipLaunchKernelGGL(k_top2_fold, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, nb, top2, folded);
+	hipLaunchKernelGGL(k_bound_local, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, nbx, nby, nbz, folded, acc, cnt, dt, limit, speed_factor);
 }
 
 bool launch_force_verlet(const ForceParams& p_in, hipStream_t s, uint32_t* nblocks, size_t partials_cap, BrickLists* bl) {
@@ -1333,7 +1360,7 @@ bool launch_force_verlet(const ForceParams& p_in, hipStream_t s, uint32_t* nbloc
 		hipLaunchKernelGGL(k_lj_verlet_build, dim3((uint32_t)nb), dim3(VNT), 0, s, p, nbx, nby, nbz);
 		return true;
 	}
-	if ((size_t)nb > partials_cap) return false;
+	if ((size_t)nb * VNW > partials_cap) return false;  // (VNW rows per workgroup: store_partials)
 	*nblocks = (uint32_t)nb;
 	if (p.precision == 1) {
 		if (shift) hipLaunchKernelGGL((k_force_lj_verlet_sp<true, true>), dim3((uint32_t)nb), dim3(VNT), 0, s, p, nbx, nby, nbz);
