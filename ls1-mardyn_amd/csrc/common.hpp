@@ -30,6 +30,72 @@ extern __attribute__((weak)) const int ls1hip_variant_marker;
 
 namespace ls1 {
 
+// Cross-lane step of the wave folds `for (o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o))` WITHOUT the LDS crossbar: lanes
+// < O get the value of lane + O, every other lane gets an unspecified value.  Only lane 0 of such a fold is consumed, and at
+// offset o only lanes < o feed it, so the fold keeps its association order and lane 0 its bits.  __shfl_down is ds_bpermute_b32 on
+// gfx9 — per double two LDS round trips and a wait on lgkmcnt, through an LDS the other workgroups of the CU keep busy; gfx950
+// exchanges the wave halves / the 16-lane rows in the VALU (v_permlane32_swap, v_permlane16_swap), and DPP row_shl moves a value
+// down inside a row.  The whole wave has to be active (every caller folds behind uniform control flow).
+// (-DLS1_WAVE_DOWN_SHFL, timing variants only: the __shfl_down form, for same-box A/B runs against it)
+#if defined(LS1_WAVE_DOWN_SHFL) && !defined(LS1_BUILD_VARIANT)
+#error "LS1_WAVE_DOWN_SHFL is a switch of tools/ab_variant.sh"
+#endif
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_permlane32_swap) && __has_builtin(__builtin_amdgcn_permlane16_swap) && !defined(LS1_WAVE_DOWN_SHFL)
+#define LS1_HAVE_PERMLANE_SWAP 1
+#endif
+#endif
+template <int O>
+__device__ __forceinline__ double wave_down_f64(double v) {
+	static_assert(O == 32 || O == 16 || O == 8 || O == 4 || O == 2 || O == 1, "offsets of the wave fold");
+#if defined(LS1_WAVE_DOWN_SHFL)
+	return __shfl_down(v, O);
+#else
+	const int lo = __double2loint(v), hi = __double2hiint(v);
+	if constexpr (O >= 16) {
+#if defined(LS1_HAVE_PERMLANE_SWAP)
+		// {vdst, src} = {v, v}: the swap exchanges lanes 32-63 (O = 16: the odd rows) of vdst with lanes 0-31 (the even rows) of
+		// src, after which src holds the upper half's (the next row's) value in its lower half (its even rows)
+		if constexpr (O == 32) {
+			const auto l = __builtin_amdgcn_permlane32_swap((unsigned)lo, (unsigned)lo, false, false);
+			const auto h = __builtin_amdgcn_permlane32_swap((unsigned)hi, (unsigned)hi, false, false);
+			return __hiloint2double((int)h[1], (int)l[1]);
+		} else {
+			const auto l = __builtin_amdgcn_permlane16_swap((unsigned)lo, (unsigned)lo, false, false);
+			const auto h = __builtin_amdgcn_permlane16_swap((unsigned)hi, (unsigned)hi, false, false);
+			return __hiloint2double((int)h[1], (int)l[1]);
+		}
+#else
+		return __shfl_down(v, O);
+#endif
+	} else {
+		// row_shl:O — lane i of a row of 16 reads lane i + O of the same row (lanes without a source keep their own value)
+		const int rl = __builtin_amdgcn_update_dpp(lo, lo, 0x100 + O, 0xf, 0xf, false);
+		const int rh = __builtin_amdgcn_update_dpp(hi, hi, 0x100 + O, 0xf, 0xf, false);
+		return __hiloint2double(rh, rl);
+	}
+#endif
+}
+// the two folds every reduction kernel uses (lane 0 holds the result)
+__device__ __forceinline__ double wave_fold_sum(double v) {
+	v += wave_down_f64<32>(v);
+	v += wave_down_f64<16>(v);
+	v += wave_down_f64<8>(v);
+	v += wave_down_f64<4>(v);
+	v += wave_down_f64<2>(v);
+	v += wave_down_f64<1>(v);
+	return v;
+}
+__device__ __forceinline__ double wave_fold_max(double v) {
+	v = fmax(v, wave_down_f64<32>(v));
+	v = fmax(v, wave_down_f64<16>(v));
+	v = fmax(v, wave_down_f64<8>(v));
+	v = fmax(v, wave_down_f64<4>(v));
+	v = fmax(v, wave_down_f64<2>(v));
+	v = fmax(v, wave_down_f64<1>(v));
+	return v;
+}
+
 // The 64-byte per-step record of the multi-site pair-stream force pass (kernels_force_mslist.hip): {x, y, z, component id, q0, q1,
 // q2, q3 (normalised once per molecule and step: FullMolecule::setupSoACache normalises q before rotating, FullMolecule.cpp:720)}.  Written by k_msl_pack and by the rigid-body kick + drift passes (IntegArgs::pk) — ONE body, contraction off, so that the
 // record is the same bits whichever pass wrote it.

@@ -21,14 +21,9 @@ namespace ls1 {
 
 constexpr int FTPB = 128;
 
-__device__ __forceinline__ double wave_max(double v) {
-	for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o));
-	return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;
-}
+// (the shfl_down tree without LDS: common.hpp, wave_down_f64)
+__device__ __forceinline__ double wave_max(double v) { return wave_fold_max(v); }
+__device__ __forceinline__ double wave_sum(double v) { return wave_fold_sum(v); }
 
 // block reduction of 4 doubles -> partials[blockIdx.x][4]
 __device__ __forceinline__ void block_reduce4(double v0, double v1, double v2, double v3, double* partials, int nwaves) {

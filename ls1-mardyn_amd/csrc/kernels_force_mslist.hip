@@ -123,10 +123,7 @@ __device__ __forceinline__ bool msl_run_sums(int key, double (&val)[N]) {
 	return msl_dpp_i<0x101>(-2, key) != key;  // row_shl:1: the next lane of the row (none: the lane ends its row)
 }
 
-__device__ __forceinline__ double msl_wave_sum_d(double v) {
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;
-}
+__device__ __forceinline__ double msl_wave_sum_d(double v) { return wave_fold_sum(v); }
 
 // Visit every molecule j != p of the 27 cells around p's cell with centre distance < rcl (list cutoff).  The three cells of an
 // x row are neighbours in the cell table; where their molecule ranges are contiguous in memory (all owned or all halo cells:
@@ -610,7 +607,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
 				msl_write_record(P.msl_pk_out, p, st.x, st.y, st.z, st.q[0], st.q[1], st.q[2], st.q[3], true, c);
 			}
 		}
-		for (int o = 32; o > 0; o >>= 1) v2max = fmax(v2max, __shfl_down(v2max, o));
+		v2max = wave_fold_max(v2max);
 		if (lane == 0) P.msl_vmax[grp] = v2max;
 		integrated = true;
 	} else if (P.fuse == 2) {

@@ -197,14 +197,8 @@ __device__ __forceinline__ void v_pair_scale(VAcc& a, double eps24) {
 	a.vir *= eps24;
 }
 
-__device__ __forceinline__ double v_wave_sum(double v) {
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;
-}
-__device__ __forceinline__ double v_wave_max(double v) {
-	for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o));
-	return v;
-}
+__device__ __forceinline__ double v_wave_sum(double v) { return wave_fold_sum(v); }
+__device__ __forceinline__ double v_wave_max(double v) { return wave_fold_max(v); }
 
 // LDS-only barrier: the brick pipeline's barriers order LDS traffic, never global memory, so they must not drain the
 // loads in flight for the next brick (a __syncthreads() would wait for every outstanding global access first)
@@ -504,20 +498,30 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 // the pair loop, no serial pass of thread 0 over the waves while the workgroup's LDS and registers stay allotted.  The consumers
 // (k_force_reduce1 with rows = VNW; k_top2_fold) fold the rows of a workgroup in the fixed order 0 .. VNW - 1, the order thread 0
 // used to fold them in: the sums keep their bits.
+template <int O>
+__device__ __forceinline__ void partials_step(double& u, double& v, double& kn, double& a, double& b) {
+	const double u2 = wave_down_f64<O>(u), v2 = wave_down_f64<O>(v), k2 = wave_down_f64<O>(kn), a2 = wave_down_f64<O>(a), b2 = wave_down_f64<O>(b);
+	u += u2;
+	v += v2;
+	kn += k2;
+	b = fmax(fmin(a, a2), fmax(b, b2));
+	a = fmax(a, a2);
+}
 __device__ __forceinline__ void store_partials(const ForceParams& P, const Totals& tot, int brick_id = -1) {
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	// every ordered pair contributes half of the pair's U and virial (see kernels_force.hip); the two largest |v_drift|^2 of the
 	// wave (local rebuild criterion) are reduced in the same steps — as an extra loop behind the sums their six dependent
 	// cross-lane exchanges sat on the tail of every workgroup (+ 0.2 ms per pass at 10^8)
+	// The exchanges stay in the VALU (wave_down_f64: permlane swaps and DPP, no ds_bpermute): six dependent LDS round trips per
+	// wave, through an LDS the other workgroup's gathers keep busy, were the rest of that chain.  Same tree, same operand order:
+	// lane 0's sums keep their bits.
 	double u = 0.5 * tot.u6, v = 0.5 * tot.vir, kn = tot.kin, a = tot.vmax2, b = tot.vmax2b;
-	for (int o = 32; o > 0; o >>= 1) {
-		const double u2 = __shfl_down(u, o), v2 = __shfl_down(v, o), k2 = __shfl_down(kn, o), a2 = __shfl_down(a, o), b2 = __shfl_down(b, o);
-		u += u2;
-		v += v2;
-		kn += k2;
-		b = fmax(fmin(a, a2), fmax(b, b2));
-		a = fmax(a, a2);
-	}
+	partials_step<32>(u, v, kn, a, b);
+	partials_step<16>(u, v, kn, a, b);
+	partials_step<8>(u, v, kn, a, b);
+	partials_step<4>(u, v, kn, a, b);
+	partials_step<2>(u, v, kn, a, b);
+	partials_step<1>(u, v, kn, a, b);
 	if (lane == 0) {
 		double* out = P.partials + ((size_t)blockIdx.x * VNW + (size_t)wv) * 4;
 		out[0] = u;
@@ -987,7 +991,10 @@ __global__ void __launch_bounds__(VNT, 4) k_force_lj_verlet(ForceParams P, int n
 	uint32_t* const rec = P.vl_rec + (size_t)did * VREC;
 	// the record's three scalars (region total, owned count, flags; uniform addresses = scalar loads).  Forcing them out at the
 	// head (inline asm) and requesting all kernel arguments of the later phases in one batch was measured: no gain (± 0.3 %) —
-	// the other workgroup of the CU hides scalar round trips of this size
+	// the other workgroup of the CU hides scalar round trips of this size.  Not loading the head's arguments at all (launch size, brick
+	// count and the five list arrays as leading arguments preloaded into SGPRs, -amdgpu-kernarg-preload-count: no kernarg load ahead of
+	// the record's in the ISA) was measured as well: − 0.02 … − 0.03 ms, inside the spread on one of two boxes — dropped
+	// (profiles/ab_kernarg_preload.txt)
 	const uint32_t rec_total = rec[VNRC], rec_ni = rec[VREC_NI], rec_flags = rec[VREC_FLAGS];
 	// own LDS slot / global index of the first pass, issued together with the list head and the flags (reads of valid memory
 	// whatever the flags say): nothing the pair loop needs is requested after the staging barrier
