@@ -219,6 +219,23 @@ struct Totals {
 };
 
 __device__ __forceinline__ uint64_t load_row(const uint64_t* p) { return *p; }
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// Row walk of ONE tile's list with the wave-uniform part of every address on the scalar unit: `tile` = first word of the tile
+// (wave-uniform: an SGPR pair), `off` = the lane's byte offset inside a row (one 32-bit VGPR, formed once per tile).  The row term
+// r * 512 B of a wave-uniform r is SALU and the load takes the scalar-base form (global_load_dwordx2 v, v_off, s[base:base+1]);
+// formed per lane as wp + r * 64 it was v_min_u32 + v_lshlrev_b64 + v_lshl_add_u64 per row load, in the pair loop.
+__device__ __forceinline__ uint64_t load_row_at(const uint64_t* tile, uint32_t row_bytes, uint32_t& off) {
+	// Two empty asm statements keep the compiler from undoing the split.  The base passes through an SGPR constraint: uniform by
+	// construction and opaque — otherwise the sum is re-associated to (tile + off) + row_bytes, a 64-bit VGPR address with a
+	// v_lshl_add_u64 per load.  The offset is tied to row_bytes: its zero extension then stays in the block of the load, where
+	// instruction selection can fold it — hoisted out of the loop it arrives as a 64-bit VGPR pair and the add stays on the VALU.
+	// `off` is passed by reference so that the statement rewrites the caller's register in place (by value: a v_mov per load).
+	typedef const __attribute__((address_space(1))) char* gbytes;
+	gbytes b = (gbytes)tile + row_bytes;
+	asm("" : "+s"(b));
+	asm("" : "+v"(off) : "s"(row_bytes));
+	return *reinterpret_cast<const __attribute__((address_space(1))) uint64_t*>(b + off);
+}
 
 __device__ __forceinline__ ListHead load_list_head(const ForceParams& P, int brick_id, int wv, int lane) {
 	const size_t t0 = (size_t)brick_id * VMAXT + (size_t)wv;
@@ -263,7 +280,9 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 	for (uint32_t base = 0, pass = 0; base < n_i; base += NT, ++pass) {
 		const uint32_t it = base + (uint32_t)tid;
 		bool active = it < n_i;
-		const uint32_t tile = pass * NW + (uint32_t)wv;  // wave-uniform
+		// wave-uniform, and told so: the tile's row count, loop index and list base then stay in SGPRs through the pair loop
+		const uint32_t wv_u = uniform_u32((uint32_t)wv);
+		const uint32_t tile = pass * NW + wv_u;
 		const bool listed = staged && tile < (uint32_t)VMAXT;
 		const size_t tile_g = (size_t)brick_id * VMAXT + tile;
 		uint32_t ii = total, gi = 0;
@@ -275,7 +294,7 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 		const bool split = pass != 0 && fast_ii != nullptr;
 		uint32_t sp_m = 0, sp_s = 0, sp_lg = 0, sp_nw = 4u;  // molecule and share of this lane, log2 of the lanes per molecule
 		if (split) {
-			const uint32_t wbase = base + (uint32_t)wv * 64u;
+			const uint32_t wbase = base + wv_u * 64u;  // (uniform like n_u: the lanes per molecule and the trip count are scalars)
 			const uint32_t n_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_i);
 			if (wbase >= n_u) continue;  // wave-uniform: this wave has no molecule in the tile
 			const uint32_t left = min(64u, n_u - wbase);
@@ -318,20 +337,29 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 		else if (listed) nw = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pass == 0 ? head.nw : (uint32_t)P.vl_nw[tile_g]));
 		if (split) {
 			const double xi = sx[VPS * ii], yi = sy[VPS * ii], zi = sz[VPS * ii];  // lanes without a molecule: the dummy slot, dummy words
-			const uint64_t* const wpm = P.vl_words + tile_g * VMAXW * 64 + sp_m;
+			const uint64_t* const tile_words = P.vl_words + tile_g * VMAXW * 64;  // wave-uniform
 			const char* const sxb = reinterpret_cast<const char*>(sx);
 			const uint64_t dummy = (uint64_t)(total * (uint32_t)VES) * 0x0001000100010001ull;
-			const uint32_t st = 1u << sp_lg, lastw = nw - 1u, trips = (nw + st - 1u) >> sp_lg;
-			uint32_t w0 = sp_s, w1 = sp_s + st;
-			// two rows in flight, one loop-carried register each (see below); rows past the end: clamped load, dummy word
-			uint64_t c0 = load_row(wpm + (size_t)min(w0, lastw) * 64), c1 = load_row(wpm + (size_t)min(w1, lastw) * 64);
+			const uint32_t st = 1u << sp_lg, trips = (nw + st - 1u) >> sp_lg;
+			// A lane's rows w = s, s + S, ... are walked as byte offsets from the tile's first word, o = w * 512 + m * 8 (one 32-bit
+			// VGPR per row register, advanced by the wave-uniform 2 S * 512): the clamp to the last row and the test w < nw are
+			// comparisons of o with the same expression at w = nw - 1 and w = nw (m * 8 < 512: the order of o is the order of w)
+			const uint32_t om = sp_m * 8u, olast = (nw - 1u) * 512u + om, oend = nw * 512u + om, ostep = st * 1024u;
+			uint32_t o0 = sp_s * 512u + om, o1 = o0 + st * 512u;
+			// two rows in flight; rows past the end: clamped load, dummy word
+			auto row_at = [&](uint32_t o) {
+				uint32_t oc = min(o, olast);
+				return load_row_at(tile_words, 0u, oc);
+			};
+			// (the second row is requested at the head of the trip that consumes it, like the fourth row of the loop below)
+			uint64_t c0 = row_at(o0);
 			for (uint32_t k = 0; k < trips; k += 2) {
-				pairs_of_word<SHIFT, SIG1>(sxb, xi, yi, zi, w0 < nw ? c0 : dummy, rc2, sig2, acc);
-				w0 += 2u * st;
-				c0 = load_row(wpm + (size_t)min(w0, lastw) * 64);
-				if (k + 1 < trips) pairs_of_word<SHIFT, SIG1>(sxb, xi, yi, zi, w1 < nw ? c1 : dummy, rc2, sig2, acc);
-				w1 += 2u * st;
-				c1 = load_row(wpm + (size_t)min(w1, lastw) * 64);
+				const uint64_t c1 = row_at(o1);
+				pairs_of_word<SHIFT, SIG1>(sxb, xi, yi, zi, o0 < oend ? c0 : dummy, rc2, sig2, acc);
+				o0 += ostep;
+				c0 = row_at(o0);
+				if (k + 1 < trips) pairs_of_word<SHIFT, SIG1>(sxb, xi, yi, zi, o1 < oend ? c1 : dummy, rc2, sig2, acc);
+				o1 += ostep;
 			}
 			// the shares of a molecule: lanes m, m + 64 / S, ... (fixed order: the same bits on every run)
 			if (sp_lg >= 1u) {
@@ -360,19 +388,22 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 			}
 		} else if (nw != 0xffu) {
 			const double xi = sx[VPS * ii], yi = sy[VPS * ii], zi = sz[VPS * ii];  // inactive lanes: the dummy slot (their words are all dummies)
-			const uint64_t* const wp = P.vl_words + tile_g * VMAXW * 64 + lane;
+			const uint64_t* const tile_words = P.vl_words + tile_g * VMAXW * 64;  // wave-uniform
+			uint32_t loff = (uint32_t)lane * 8u;  // the lane's place in every row (never changed: see load_row_at)
+			auto row = [&](uint32_t r) { return load_row_at(tile_words, r * 512u, loff); };  // r wave-uniform: SALU
 			const char* const sxb = reinterpret_cast<const char*>(sx);
 			// Four word rows in flight (a row comes from HBM more often than from L2: the lists are read once per step).  Each
-			// row register is reloaded right after its content is consumed — ONE loop-carried value per row: with a rotating
+			// row register is reloaded right after its content is consumed (the fourth: at the head of the next trip, see the loop)
+			// — ONE value per row, never handed from register to register: with a rotating
 			// window (w0 <- w1 <- w2 <- w3) the compiler sank every load to its use and waited vmcnt(0) on it, i.e. a dependent
 			// HBM round trip per four pairs; a load inside a branch has the same effect (seen in the ISA).
 			const uint32_t last = LS1_HOOK_LAST_ROW(nw);  // nw - 1 (nw >= 4: rows are dummy-padded by the build)
 			uint64_t r0 = head.w0, r1 = head.w1;  // first tile: loaded ahead by the caller (rows 0 and 1)
 			if (pass != 0) {
-				r0 = load_row(wp);
-				r1 = load_row(wp + 64);
+				r0 = row(0u);
+				r1 = row(1u);
 			}
-			uint64_t r2 = load_row(wp + 128), r3 = load_row(wp + 192);
+			uint64_t r2 = row(2u);
 			auto four_pairs = [&](uint64_t cur) {
 				const uint32_t lo32 = (uint32_t)cur, hi32 = (uint32_t)(cur >> 32);
 				const uint32_t o0 = lo32 & 0xffffu, o1 = lo32 >> 16, o2 = hi32 & 0xffffu, o3 = hi32 >> 16;
@@ -390,14 +421,18 @@ __device__ __forceinline__ void brick_forces(const ForceParams& P, const BrickTa
 			nw = LS1_HOOK_ROWS(nw);  // (nw)
 			for (uint32_t k = 0; k < nw; k += 4) {
 				// rows past the end are clamped to the last row and evaluated as what they are after the clamp: skipped
+				// (k, nw and last are wave-uniform: the row index and the three tests are scalar code, EXEC is not touched)
+				// The fourth row is requested at the head of the trip that consumes it (three trips' quarters ahead of its use, like
+				// the others).  Written as the last statement of the body, next to a copy in front of the loop, the two loads were
+				// merged into one at the loop head anyway — with its address formed in another block, on the VALU
+				const uint64_t r3 = row(min(k + 3u, last));
 				four_pairs(r0);
-				r0 = load_row(wp + (size_t)min(k + 4u, last) * 64);
+				r0 = row(min(k + 4u, last));
 				if (k + 1 < nw) four_pairs(r1);
-				r1 = load_row(wp + (size_t)min(k + 5u, last) * 64);
+				r1 = row(min(k + 5u, last));
 				if (k + 2 < nw) four_pairs(r2);
-				r2 = load_row(wp + (size_t)min(k + 6u, last) * 64);
+				r2 = row(min(k + 6u, last));
 				if (k + 3 < nw) four_pairs(r3);
-				r3 = load_row(wp + (size_t)min(k + 7u, last) * 64);
 			}
 		} else if (active && staged) {
 			// no stored list for this tile (list overflow, or more owned molecules than the list capacity covers)
