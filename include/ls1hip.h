@@ -368,6 +368,59 @@ int ls1hip_rdf_reset(ls1hip_ctx* ctx);
  * positions of that step's force evaluation, directly before the force pass, on the step's regenerated or refreshed halo; the
  * trajectory does not change. */
 
+/* ---- spatial profiles ----------------------------------------------------------------------------------------------
+ * The reference's SpatialProfile plugin (plugins/SpatialProfile.{h,cpp}) with the profiles of plugins/profiles/: per bin of a
+ * Cartesian or cylindrical sampling grid over the GLOBAL box the number of molecules and, on request, sums of |v|, v, 3 + rotDOF,
+ * m v^2 + I w^2 and the per-molecule virial.  The accumulators are global (one entry per bin of the whole box) and live on the
+ * device; every rank counts its OWNED molecules only, never halo copies, so the sum of the tables over the ranks is what the
+ * reference's collCommAllreduceSum delivers (SpatialProfile.cpp:286-310).
+ * Bin index (SpatialProfile::init, getCartesianUID, getCylUID; SpatialProfile.cpp:146-222, 339-410), operation for operation:
+ *   Cartesian  inv[d] = units[d] / global_len[d];  uID = floor(x inv0) ny nz + floor(y inv1) nz + floor(z inv2);
+ *   cylinder   centre (Lx/2, 0, Lz/2), R2max = 0.24 min(Lx, Lz)^2, inv = (nR / R2max, nH / Ly, nPhi / 2 pi),
+ *              phi = atan2(zc, xc) (+ 2 pi when negative), uID = hUn nR nPhi + rUn nPhi + phiUn; molecules with rUn >= nR are
+ *              skipped.
+ * Coordinates are the global ones wrapped into [0, L): between two builds of the neighbour lists a molecule may sit up to
+ * skin / 2 outside the box and is binned where ls1hip_download_state reports it.  DEVIATION: an index that rounds to n at the
+ * upper face of the box is clamped to n - 1 (the reference writes such a molecule into a map entry no writer reads).
+ * Summation order: the u64 counts are exact; the f64 sums are accumulated with atomic adds whose arrival order is not fixed, so
+ * they may differ in the last bits from run to run. */
+#define LS1HIP_PROF_CARTESIAN 0
+#define LS1HIP_PROF_CYLINDER  1
+/* quantities (bit mask); the molecule count N is always sampled (DensityProfile.h:19-21) */
+#define LS1HIP_PROF_VELOCITY    1   /* sum |v|              VelocityAbsProfile.h:22-31                    */
+#define LS1HIP_PROF_VELOCITY3D  2   /* sum v[3]             Velocity3dProfile.h:24-28                     */
+#define LS1HIP_PROF_TEMPERATURE 4   /* sum (3 + rotDOF) as u64, sum (m v^2 + I w^2)   DOFProfile.h:18-20, KineticProfile.h:17-22 */
+#define LS1HIP_PROF_VIRIAL      8   /* sum Vi[3]            VirialProfile.h:27-31                         */
+/* SpatialProfile::readXML + init (SpatialProfile.cpp:22-222): units = (x, y, z) bins in Cartesian mode, (r, h, phi) in cylinder
+ * mode; component = -1 samples every component, otherwise the 0-based component id (the reference's XML value is 1-based and
+ * compared as componentid() == _profiledComp - 1, SpatialProfile.cpp:244).  units = {0, 0, 0}: sampling off, buffers freed.
+ * Needs components and domain.  LS1HIP_EINVAL: a zero unit among non-zero ones, bins x words per bin above the 32-bit index, an
+ * unknown mode or quantity bit, a component id outside the component set.  Tables start at zero. */
+int ls1hip_profile_config(ls1hip_ctx* ctx, int mode, const uint32_t units[3], unsigned quantities, int component);
+/* Bins and quantity mask of the current configuration (0, 0 when off): _uIDs of SpatialProfile.cpp:189-190. */
+int ls1hip_profile_layout(const ls1hip_ctx* ctx, size_t* bins, unsigned* quantities);
+/* The molecule loop of SpatialProfile::endStep (SpatialProfile.cpp:238-283): one pass over the owned molecules, on the CURRENT
+ * positions and velocities wherever the engine keeps them; adds 1 to the sample counter (_accumulatedDatasets).  The caller is
+ * responsible for full-step velocities (the reference samples after the post-force kick and after the thermostat,
+ * Simulation.cpp:1099-1131, 1223).  Refused instead of sampling a wrong state: after a fused force + integration pass
+ * (velocities half a step ahead, positions parked), while a split pass is in flight, and LS1HIP_PROF_VIRIAL without option
+ * compute_vi = 1 and valid forces.  m v^2 and I w^2 are the terms of ls1hip_kinetic_sums_by_component; rotDOF comes from the
+ * component table (ls1hip_set_rot_dof).  Timer "profile". */
+int ls1hip_profile_sample(ls1hip_ctx* ctx);
+/* LOCAL tables of this rank (the operands of collectAppend, SpatialProfile.cpp:293-297); any pointer may be NULL, one that is
+ * not needs its quantity configured; n, dof, ekin, vabs: [bins]; v3, vi3: [bins][3]; cap_bins: entries the buffers hold;
+ * *samples = ls1hip_profile_sample passes since the last reset. */
+int ls1hip_profile_read(ls1hip_ctx* ctx, size_t cap_bins, uint64_t* n, uint64_t* dof, double* ekin, double* vabs, double* v3,
+						double* vi3, uint64_t* samples);
+/* ProfileBase::reset of every bin and _accumulatedDatasets = 0 (SpatialProfile.cpp:320-326). */
+int ls1hip_profile_reset(ls1hip_ctx* ctx);
+/* Options "profile_every" (default 0 = never) and "profile_from" (default 0): ls1hip_run samples on every step s with
+ * s >= profile_from && s % profile_every == 0, s counted as for "rdf_every" (simstep >= _initStatistics && simstep %
+ * _profileRecordingTimesteps == 0, SpatialProfile.cpp:238).  The sample is taken AFTER that step's post-force kick; with the
+ * device thermostat it bins beta_trans v and beta_rot D with the factors the kick's reduction left on the device — the scaled
+ * velocities the reference's endStep sees — without touching the state.  A sampling step takes the loop's unfused route (as the
+ * last step of a call does); per-step loops keep their trajectory bit for bit, list loops may move a rebuild. */
+
 /* ---- multi-GPU plumbing: packed buffers a host transport (RCCL via torch.distributed, MPI, ...) moves ---------
  * Wire formats (little endian, FP64): leaving molecule = 15 doubles {id(as bits), cid(as bits), r3, v3, q4, D3}
  * (the reference's 116-byte record, parallel/CommunicationBuffer.cpp:131-145, padded to 120); halo molecule =
@@ -409,7 +462,8 @@ int ls1hip_soa_forces(ls1hip_ctx* ctx, const int cell_dims[3], const uint32_t* c
 
 /* Device time (ms, HIP events on the context's compute stream) and launch count accumulated per kernel class
  * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction),
- * "rdf" (RDF sampling pass)}. */
+ * "rdf" (RDF sampling pass),
+ * "profile" (profile sampling pass)}. */
 int ls1hip_timing(ls1hip_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int ls1hip_timing_reset(ls1hip_ctx* ctx);
 /* Per-launch HIP-event timing: 0 = off, 1 = every phase, 2 = force passes only (each timed scope puts two event markers

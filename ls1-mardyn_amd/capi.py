@@ -75,6 +75,11 @@ SYMBOLS = {
     "ls1hip_rdf_sample": (C.c_int, [C.c_void_p]),
     "ls1hip_rdf_read": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, _u64p, C.c_size_t, _u64p, _u64p]),
     "ls1hip_rdf_reset": (C.c_int, [C.c_void_p]),
+    "ls1hip_profile_config": (C.c_int, [C.c_void_p, C.c_int, _u32p, C.c_uint, C.c_int]),
+    "ls1hip_profile_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]),
+    "ls1hip_profile_sample": (C.c_int, [C.c_void_p]),
+    "ls1hip_profile_read": (C.c_int, [C.c_void_p, C.c_size_t, _u64p, _u64p, _dp, _dp, _dp, _dp, _u64p]),
+    "ls1hip_profile_reset": (C.c_int, [C.c_void_p]),
     "ls1hip_export_counts": (C.c_int, [C.c_void_p, C.c_int, _u64p]),
     "ls1hip_export_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "ls1hip_export_pack_dirs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t]),

@@ -62,6 +62,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	dfree(c->d_stage);
 	dfree(c->d_steplog);
 	rdf_destroy(c);
+	profile_destroy(c);
 	if (c->d_ingest) hipFree(c->d_ingest);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_flag) hipHostFree((void*)c->h_flag);
@@ -125,6 +126,12 @@ extern "C" int ls1hip_set_option(ls1hip_ctx* c, const char* name, long v) {
 	} else if (n == "rdf_every") {
 		REQUIRE(c, v >= 0, "rdf_every must be >= 0 (0: ls1hip_run does not sample)");
 		c->opt_rdf_every = v;
+	} else if (n == "profile_every") {
+		REQUIRE(c, v >= 0, "profile_every must be >= 0 (0: ls1hip_run does not sample)");
+		c->opt_profile_every = v;
+	} else if (n == "profile_from") {
+		REQUIRE(c, v >= 0, "profile_from must be >= 0");
+		c->opt_profile_from = v;
 	} else if (n == "lj_split") {
 		REQUIRE(c, v == 0 || v == 1 || v == 2 || v == 4 || v == 5 || v == 6, "lj_split must be 0 (auto), 1, 2 (list kernel lanes per molecule), 4, 5 or 6 (MFMA pre-filter variants)");
 		c->opt_lj_split = v;
@@ -148,6 +155,8 @@ extern "C" int ls1hip_get_option(const ls1hip_ctx* c, const char* name, long* v)
 	else if (n == "precision") *v = c->opt_precision;
 	else if (n == "local_rebuild") *v = c->opt_local_rebuild;
 	else if (n == "rdf_every") *v = c->opt_rdf_every;
+	else if (n == "profile_every") *v = c->opt_profile_every;
+	else if (n == "profile_from") *v = c->opt_profile_from;
 	else if (n == "verlet_irregular_bricks") {
 		// bricks of the last list build that do NOT run the production path of the list force pass (region beyond the LDS staging
 		// area, list overflow, more owned molecules than the tiles cover): read back from the device on request, any precision
@@ -560,6 +569,7 @@ extern "C" int ls1hip_upload_begin(ls1hip_ctx* c, size_t n) {
 	c->n_real = 0;
 	c->n_halo = 0;
 	c->binned = c->halo_valid = c->forces_valid = false;
+	c->half_advanced = false;
 	c->msl_pk_fresh = false;
 	c->pos_x = c->pos_y = c->pos_z = nullptr;
 	c->vl_ready = false;
@@ -861,6 +871,7 @@ static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
 	if (n == "build") return &c->t_build;
 	if (n == "halo") return &c->t_halo;
 	if (n == "rdf") return &c->t_rdf;
+	if (n == "profile") return &c->t_profile;
 	return nullptr;
 }
 
@@ -877,7 +888,7 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
-	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf}) {
+	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile}) {
 		timer_collect(*t);
 		t->total_ms = 0;
 		t->launches = 0;

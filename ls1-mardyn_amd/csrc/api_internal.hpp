@@ -1,4 +1,4 @@
-// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling;
+// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling; api_profile.hip: spatial profiles;
 // api_step.hip: the pieces of a time step, neighbour lists, ls1hip_run; api_exchange.hip: long-range correction, export / import of
 // the multi-rank exchange, seam A).  Round 4: split out of one 2 400-line api.hip; nothing here is exported from the
 // library (LS1_INTERNAL = hidden visibility).
@@ -144,3 +144,7 @@ LS1_INTERNAL void macro_to_upot_virial(const DevCounters* h, double* upot, doubl
 LS1_INTERNAL int materialise_positions(ls1hip_ctx* c);
 LS1_INTERNAL int rdf_sample_impl(ls1hip_ctx* c);  // api_rdf.hip: one RDF traversal (ls1hip_rdf_sample; ls1hip_run with "rdf_every")
 LS1_INTERNAL void rdf_destroy(ls1hip_ctx* c);
+// api_profile.hip: one profile sampling pass (ls1hip_profile_sample; ls1hip_run with "profile_every"); scaled: bin the velocities
+// multiplied by the thermostat factors on the device
+LS1_INTERNAL int profile_sample_impl(ls1hip_ctx* c, bool scaled);
+LS1_INTERNAL void profile_destroy(ls1hip_ctx* c);

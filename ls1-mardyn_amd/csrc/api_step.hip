@@ -328,7 +328,10 @@ extern "C" int ls1hip_forces(ls1hip_ctx* c, int which, double* upot, double* vir
 		if ((rc = launch_forces(c, which))) return rc;
 	}
 	if (which == 1) c->inner_in_flight = !c->halo_valid;  // halo already populated (old call order): nothing to overlap
-	if (which != 1) c->forces_valid = true;
+	if (which != 1) {
+		c->forces_valid = true;
+		c->half_advanced = false;
+	}
 	if (upot || virial) {
 		int rc = sync_counters(c);
 		if (rc) return rc;
@@ -362,6 +365,7 @@ extern "C" int ls1hip_forces_kick_drift(ls1hip_ctx* c, int which, double dt, dou
 		c->binned = false;
 		c->halo_valid = false;
 		c->forces_valid = false;
+		c->half_advanced = true;
 		c->msl_pk_fresh = false;
 	}
 	if (upot || virial) {
@@ -917,10 +921,12 @@ static int forces_list_impl(ls1hip_ctx* c, int which, double dt, bool post_kick,
 		c->vl_bound_pending = true;
 		c->halo_valid = false;
 		c->forces_valid = false;
+		c->half_advanced = true;
 		c->msl_pk_fresh = !c->one_clj;
 		c->vl_steps++;
 	} else {
 		c->forces_valid = true;
+		c->half_advanced = false;
 		c->vl_steps++;
 	}
 	if (upot || virial) {
@@ -967,6 +973,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	REQUIRE(c, !c->has_remote, "ls1hip_run drives single-rank domains only (use the piecewise calls with a transport)");
 	REQUIRE(c, c->forces_valid, "initial forces required (rebin, halo, forces) before ls1hip_run");
 	REQUIRE(c, !c->opt_rdf_every || c->rdf_bins > 0, "option rdf_every is set but RDF sampling is not configured (ls1hip_rdf_config)");
+	REQUIRE(c, !c->opt_profile_every || c->prof_bins > 0, "option profile_every is set but profile sampling is not configured (ls1hip_profile_config)");
 	HIPCHK(c, hipSetDevice(c->device));
 	// Between two steps of an NVE run on the LJ fast path the force pass does the integration itself (fused mode, the
 	// reference's reduced-memory scheme); the last step is unfused so that F and the kinetic sums are available.
@@ -976,6 +983,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	// the single-centre list pass does the post-force kick (+ sum m v^2) itself; the multi-site one leaves it to the integrator passes
 	const bool list_kick = verlet && (c->one_clj || (can_list_ms(c) && can_list_kick_ms(c)));
 	bool advanced = false;  // the previous force pass already did kick + kick + drift
+	bool kicked = false;    // the previous step sampled profiles: its post-force kick (+ kinetic sums, betas) is done
 	// step log: one row {U_pot, virial, sum m v^2, sum I w^2, N, rotDOF} per step, written by the reductions on the device
 	if (!c->d_steplog) {
 		int rc0 = dalloc(c, &c->d_steplog, STEPLOG_ROWS * 6);
@@ -1000,19 +1008,25 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			// passes: kick (+ sums, betas on the device) -> scale -> kick+drift   (Simulation.cpp:1099-1131)
 			// (the scaling itself is folded into the kick + drift pass, with the betas the kick's reduction left on the device)
 			// In list mode the force pass of step s-1 has done the post-force kick and the kinetic sum (betas on the device).
-			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
+			if (!list_kick && !kicked && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
 			if ((rc = kick_drift_impl(c, dt, 2, 1., 1.))) return rc;
-		} else if (list_kick) {
+		} else if (list_kick || kicked) {
 			if ((rc = ls1hip_kick_drift(c, dt))) return rc;  // (post-force kick already done by the list force pass)
 		} else {
 			// post-force kick of step s-1 fused with the pre-force kick+drift of step s (same F, one pass)
 			if ((rc = ls1hip_kick_then_kick_drift(c, dt))) return rc;
 		}
-		advanced = fuse && s + 1 < nsteps;
+		kicked = false;
+		const unsigned long simstep = ++c->run_step;
+		// SpatialProfile::endStep (SpatialProfile.cpp:238): simstep >= _initStatistics && simstep % _profileRecordingTimesteps == 0
+		// samples the state at the END of the step — full-step velocities, after the thermostat.  Such a step goes the unfused way
+		// (as the last one does): force pass, post-force kick, sampling pass; the head of the next step then only drifts.
+		const bool prof_now = c->opt_profile_every > 0 && simstep >= (unsigned long)c->opt_profile_from &&
+							  simstep % (unsigned long)c->opt_profile_every == 0;
+		advanced = fuse && s + 1 < nsteps && !prof_now;
 		// RDF::afterForces (RDF.cpp:573-581): simstep % samplingfrequency == 0 samples the positions of this step's force evaluation.
 		// The pass runs directly BEFORE the force pass (a fused pass leaves the next step's positions behind), on the refreshed
 		// or regenerated halo; nothing of the step itself changes.
-		const unsigned long simstep = ++c->run_step;
 		const bool rdf_now = c->opt_rdf_every > 0 && simstep % (unsigned long)c->opt_rdf_every == 0;
 		if (verlet) {
 			// the lists, the binning and the halo slots live until the displacement bound of the molecules (accumulated on
@@ -1045,10 +1059,14 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			rc = advanced ? ls1hip_forces_kick_drift(c, 0, dt, nullptr, nullptr) : ls1hip_forces(c, 0, nullptr, nullptr);
 		}
 		if (rc) return rc;
-		if (s + 1 == nsteps) {
+		if (s + 1 == nsteps || prof_now) {
 			c->log_row_kin = c->log_row;
 			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
-			if (c->thermostat_on) {
+			// the thermostat's scaling waits for the next kick + drift pass (or the scale pass below): the sampling pass bins
+			// beta * v and beta * D with the factors the kick's reduction left on the device, the state stays as it is
+			if (prof_now && (rc = profile_sample_impl(c, c->thermostat_on))) return rc;
+			kicked = s + 1 < nsteps;
+			if (s + 1 == nsteps && c->thermostat_on) {
 				TimedScope ts(c, c->t_integrate);
 				launch_scale(integ_args(c, 0.), 1., 1., true, c->stream);
 			}

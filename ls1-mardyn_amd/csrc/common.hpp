@@ -233,6 +233,25 @@ struct RdfParams {
 	unsigned long long *g_mol, *g_site, *g_n;  // global histograms, owned molecules per component
 };
 
+// spatial profiles (kernels_profile.hip): plugins/SpatialProfile.{h,cpp}, plugins/profiles/*
+struct ProfParams {
+	int mode;           // LS1HIP_PROF_CARTESIAN / LS1HIP_PROF_CYLINDER
+	unsigned quant;     // LS1HIP_PROF_* bit mask
+	int comp;           // -1: every component, else the 0-based component id sampled
+	int ncomp;
+	int scale;          // 1: bin cnt->beta[0] * v and cnt->beta[1] * D (the scaling ls1hip_run folds into the next kick + drift)
+	uint32_t units[3], bins, words;
+	double inv[3], len[3], centre[3];  // universalInvProfileUnit, globalLength, universalCentre (SpatialProfile.cpp:146-212)
+	// word offsets of the quantity arrays in the table {n[bins] | dof[bins] | ekin[bins] | vabs[bins] | v3[bins][3] | vi3[bins][3]}
+	// (absent quantities take no room); the first u64_words words are integers, the rest doubles
+	uint32_t off_dof, off_ekin, off_vabs, off_v3, off_vi, u64_words;
+	const double *x, *y, *z, *vx, *vy, *vz, *q0, *q1, *q2, *q3, *Dx, *Dy, *Dz, *Vix, *Viy, *Viz;
+	const int32_t* cid;
+	const CompTable* ct;
+	const DevCounters* cnt;
+	unsigned long long* tab;  // global table (plain device memory)
+};
+
 struct Timer {
 	std::vector<hipEvent_t> ev;  // start/stop pairs
 	size_t used = 0;
@@ -370,6 +389,17 @@ struct ls1hip_ctx {
 	long opt_rdf_every = 0;
 	unsigned long run_step = 0;  // steps ls1hip_run has done on this context (simstep of RDF::afterForces)
 	ls1::Timer t_rdf;
+	// spatial profiles (ls1hip_profile_*; kernels_profile.hip): one device table, layout of ProfParams
+	int prof_mode = 0, prof_comp = -1;
+	unsigned prof_quant = 0;
+	uint32_t prof_units[3] = {0, 0, 0};
+	size_t prof_bins = 0, prof_words = 0;
+	unsigned long long* d_prof = nullptr;
+	uint64_t prof_samples = 0;
+	long opt_profile_every = 0, opt_profile_from = 0;
+	// a fused force + integration pass wrote the velocities last: they are half a step ahead of the positions' force evaluation
+	bool half_advanced = false;
+	ls1::Timer t_profile;
 	// streaming upload (ls1hip_upload_begin / _chunk / _records / _end)
 	bool ingest_open = false;
 	size_t ingest_total = 0, ingest_at = 0;
@@ -509,6 +539,9 @@ bool launch_force_ms_list(const ForceParams& p, bool has_rot, bool lj_only, bool
 						  const double* shift27, double* pk, hipStream_t s, uint32_t* nblocks, size_t partials_cap, bool pk_fresh = false);
 // RDF sampling pass over all bricks (kernels_rdf.hip); fills r.mol_lds / r.site_lds; false: the grid cannot be served (hw != 1)
 bool launch_rdf(const ForceParams& p, RdfParams r, bool has_rot, double mean_per_cell, hipStream_t s);
+// spatial-profile sampling pass over the owned molecules (kernels_profile.hip); n_cap: launch bound (n_real is read on the device)
+void launch_profile(const ProfParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+size_t profile_lds_words();  // largest table a workgroup keeps in LDS (above it: run-merged global atomics)
 // kin_in_slot1: the partials' slot 1 carries sum m v^2 of a fused force + integration pass (goes to cnt->kin[0], not to
 // the macroscopic sums); log (may be null): the step-log row {U_pot, virial, sum m v^2, sum I w^2, N, rotDOF} to refresh
 struct ReduceMode {

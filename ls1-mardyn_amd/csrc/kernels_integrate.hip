@@ -194,17 +194,15 @@ __global__ void __launch_bounds__(ITPB) k_kin_by_component(IntegArgs a, int ncom
 	int c = -1;
 	if (p < a.cnt->n_real) {
 		c = ncomp > 1 ? a.mol.cid[p] : 0;
-		const double m = a.ct->mass[c];
-		const double vx = a.mol.vx[p], vy = a.mol.vy[p], vz = a.mol.vz[p];
-		mv2 = m * (vx * vx + vy * vy + vz * vz);
 		rdof = (double)a.ct->rotdof[c];
 		one = 1.;
-		if (HAS_ROT) {
-			const V3 D = {a.mol.Dx[p], a.mol.Dy[p], a.mol.Dz[p]};
-			V3 w = rotate_inv(rot_of(a.mol.q0[p], a.mol.q1[p], a.mol.q2[p], a.mol.q3[p]), D);
-			w = {w.x * a.ct->invI[c][0], w.y * a.ct->invI[c][1], w.z * a.ct->invI[c][2]};
-			Iw2 = a.ct->I[c][0] * w.x * w.x + a.ct->I[c][1] * w.y * w.y + a.ct->I[c][2] * w.z * w.z;
-		}
+		// (the terms: leapfrog_body.hpp, shared with the profile sampling pass)
+		if (HAS_ROT)
+			kinetic_terms<true>(a.ct->mass[c], a.ct->I[c], a.ct->invI[c], a.mol.vx[p], a.mol.vy[p], a.mol.vz[p], a.mol.q0[p], a.mol.q1[p],
+								a.mol.q2[p], a.mol.q3[p], V3{a.mol.Dx[p], a.mol.Dy[p], a.mol.Dz[p]}, mv2, Iw2);
+		else
+			kinetic_terms<false>(a.ct->mass[c], a.ct->I[c], a.ct->invI[c], a.mol.vx[p], a.mol.vy[p], a.mol.vz[p], 1., 0., 0., 0.,
+								 V3{0., 0., 0.}, mv2, Iw2);
 	}
 	__shared__ double red[ITPB / 64][MAXC][4];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -96,4 +96,19 @@ __device__ __forceinline__ double leap_post_pre(double dt, double mass, V3 invI,
 	return vx * vx + vy * vy + vz * vz;
 }
 
+// m v^2 and I w^2 of one molecule from its current velocity / angular momentum (Molecule::calculate_mv2_Iw2,
+// FullMolecule.cpp:398-404): the body of k_kin_by_component (kernels_integrate.hip) and of the profile sampling pass
+// (kernels_profile.hip), which must agree term by term.
+template <bool HAS_ROT>
+__device__ __forceinline__ void kinetic_terms(double mass, const double I[3], const double invI[3], double vx, double vy, double vz,
+											  double q0, double q1, double q2, double q3, V3 D, double& mv2, double& Iw2) {
+	mv2 = mass * (vx * vx + vy * vy + vz * vz);
+	Iw2 = 0.;
+	if (HAS_ROT) {
+		V3 w = rotate_inv(rot_of(q0, q1, q2, q3), D);
+		w = {w.x * invI[0], w.y * invI[1], w.z * invI[2]};
+		Iw2 = I[0] * w.x * w.x + I[1] * w.y * w.y + I[2] * w.z * w.z;
+	}
+}
+
 }  // namespace ls1

@@ -473,6 +473,34 @@ def rdf_collect(engine, dist=None, group=None, device=None):
     return out
 
 
+def profile_collect(engine, dist=None, group=None, device=None):
+    """The collective of SpatialProfile::endStep (plugins/SpatialProfile.cpp:286-310): the local tables of every rank summed by
+    at most two all-reduces — one int64 block {n, dof}, one float64 block {ekin, vabs, v3, vi3} (the reference appends one value per
+    bin and profile to one collective).  Returns the dict of DeviceEngine.profile_read with global values; `samples` is this rank's
+    own (every rank samples the same steps).  Without an initialised process group: the local values."""
+    local = engine.profile_read()
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    out = dict(local)
+    for keys, dt_wire, dt_out in ((("n", "dof"), np.int64, np.uint64), (("ekin", "vabs", "v3", "vi3"), np.float64, np.float64)):
+        have = [k for k in keys if k in local]
+        if not have:
+            continue
+        t = torch.from_numpy(np.concatenate([local[k].reshape(-1) for k in have]).astype(dt_wire))
+        if device is not None:
+            t = t.to(device)
+        dist.all_reduce(t, group=group)
+        flat, at = t.cpu().numpy().astype(dt_out), 0
+        for k in have:
+            out[k] = flat[at:at + local[k].size].reshape(local[k].shape).copy()
+            at += local[k].size
+    return out
+
+
 def build_strong_scaling_box(comps, rc, n_per_dim, world, rank, local_rank, rho, temp, cic=None, kernel=0,
                              stage_through_host=False, loopback=False, options=None, skin=None):
     """bench.py helper: the GLOBAL jittered bcc liquid of 2*n^3 molecules (synth.py) split over the rank grid; every

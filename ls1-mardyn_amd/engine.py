@@ -360,6 +360,51 @@ class DeviceEngine:
     def rdf_reset(self):
         self._chk(self.lib.ls1hip_rdf_reset(self.ctx))
 
+    # -- spatial profiles (ls1hip_profile_*: the reference's SpatialProfile plugin) ---------------------------------------------
+    PROF_CARTESIAN, PROF_CYLINDER = 0, 1
+    PROF_VELOCITY, PROF_VELOCITY3D, PROF_TEMPERATURE, PROF_VIRIAL = 1, 2, 4, 8
+
+    def profile_config(self, mode: int, units, quantities: int = 0, component: int = -1):
+        """units = (x, y, z) bins (Cartesian) or (r, h, phi) (cylinder); component -1 = all, else the 0-based component id;
+        units = (0, 0, 0) switches the sampling off and frees the device tables."""
+        u = np.ascontiguousarray(units, dtype=np.uint32).reshape(3)
+        self._chk(self.lib.ls1hip_profile_config(self.ctx, int(mode), u.ctypes.data_as(capi._u32p), int(quantities), int(component)))
+
+    def profile_layout(self):
+        """(bins, quantity mask) of the current configuration; (0, 0) when off."""
+        b = C.c_size_t(); q = C.c_uint()
+        self._chk(self.lib.ls1hip_profile_layout(self.ctx, C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    def profile_sample(self):
+        """One pass over the owned molecules on the current positions and velocities, added to the device tables."""
+        self._chk(self.lib.ls1hip_profile_sample(self.ctx))
+
+    def profile_read(self):
+        """LOCAL tables of this rank: n uint64 [bins] and, for the configured quantities, dof uint64 [bins], ekin [bins],
+        vabs [bins], v3 [bins, 3], vi3 [bins, 3]; samples; quantities (the mask)."""
+        bins, q = self.profile_layout()
+        out = dict(n=np.zeros(bins, dtype=np.uint64), quantities=q)
+        if q & self.PROF_TEMPERATURE:
+            out["dof"] = np.zeros(bins, dtype=np.uint64)
+            out["ekin"] = np.zeros(bins)
+        if q & self.PROF_VELOCITY:
+            out["vabs"] = np.zeros(bins)
+        if q & self.PROF_VELOCITY3D:
+            out["v3"] = np.zeros((bins, 3))
+        if q & self.PROF_VIRIAL:
+            out["vi3"] = np.zeros((bins, 3))
+        smp = C.c_uint64()
+        u64 = lambda k: out[k].ctypes.data_as(capi._u64p) if k in out else None  # noqa: E731
+        f64 = lambda k: capi.dptr(out[k]) if k in out else None  # noqa: E731
+        self._chk(self.lib.ls1hip_profile_read(self.ctx, bins, u64("n"), u64("dof"), f64("ekin"), f64("vabs"), f64("v3"), f64("vi3"),
+                                               C.byref(smp)))
+        out["samples"] = int(smp.value)
+        return out
+
+    def profile_reset(self):
+        self._chk(self.lib.ls1hip_profile_reset(self.ctx))
+
     # -- multi-GPU plumbing -----------------------------------------------------------------------------------------
     def export_counts(self, kind: int):
         c = np.zeros(27, dtype=np.uint64)

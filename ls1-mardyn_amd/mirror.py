@@ -350,6 +350,196 @@ class RDF:
             f.write("".join(out))
 
 
+def _g6(x) -> str:
+    """operator<< of a double / long double at precision(6) (ofstream::precision(6) of every profile writer)"""
+    x = float(x)
+    if x != x:
+        return "-nan" if np.signbit(x) else "nan"
+    if np.isinf(x):
+        return "-inf" if x < 0 else "inf"
+    return "%.6g" % x
+
+
+class SpatialProfile:
+    """The reference's SpatialProfile plugin (plugins/SpatialProfile.{h,cpp}, plugins/profiles/*) over the device tables.
+    Constructor arguments = the nodes SpatialProfile::readXML reads (SpatialProfile.cpp:22-134): mode ("cartesian" / "cylinder" or
+    the LS1HIP_PROF_* value), units = (x, y, z) or (r, h, phi), writefrequency, init, recording, outputprefix, profiledComponent
+    ("all" or the 1-based component id of the XML) and profiles = the names switched on among density, velocity, velocity3d,
+    temperature, virial, virial2D; none given -> all (SpatialProfile.cpp:88-91).  The Virial2D writer does not exist here: its
+    accumulators (density, DOF, kinetic, virial) are sampled, its file is not written."""
+
+    CARTESIAN, CYLINDER = 0, 1
+
+    def __init__(self, global_length, *, mode="cartesian", units=(1, 1, 1), writefrequency: int = 1, init: int = 0, recording: int = 1,
+                 outputprefix: str = "profile", profiledComponent="all", profiles=()):
+        if mode in ("cartesian", self.CARTESIAN):
+            self._cylinder = False
+        elif mode in ("cylinder", self.CYLINDER):
+            self._cylinder = True
+        else:
+            raise ValueError("[SpatialProfile] Invalid mode. cylinder/cartesian")
+        self._units = tuple(int(u) for u in units)
+        self._writeFrequency, self._initStatistics, self._profileRecordingTimesteps = int(writefrequency), int(init), int(recording)
+        self._outputPrefix = str(outputprefix)
+        self._profiledComp = None if str(profiledComponent) == "all" else int(profiledComponent)  # 1-based, as in the XML
+        known = ("density", "velocity", "velocity3d", "temperature", "virial", "virial2D")
+        on = set(profiles)
+        if on - set(known):
+            raise ValueError("unknown profile(s): %s" % sorted(on - set(known)))
+        self._ALL = not on  # "NO PROFILES SPECIFIED -> Outputting all"
+        f = {k: (k in on) for k in known}
+        # the profiles SpatialProfile::readXML adds (SpatialProfile.cpp:93-127)
+        self._dens = f["density"] or f["velocity"] or f["velocity3d"] or f["virial"] or f["virial2D"] or self._ALL
+        self._velAbs = f["velocity"] or self._ALL
+        self._vel3d = f["velocity3d"] or self._ALL
+        self._virial = f["virial"] or self._ALL
+        self._temp = f["temperature"] or self._ALL
+        self._dofkin = self._temp or f["virial2D"]
+        # SpatialProfile::init (SpatialProfile.cpp:146-212)
+        L = self._globalLength = np.asarray(global_length, dtype=np.float64).copy()
+        u = self._units
+        if self._cylinder:
+            minXZ = min(L[0], L[2])
+            R2max = .24 * minXZ * minXZ
+            self._inv = (u[0] / R2max, u[1] / L[1], u[2] / (2 * np.pi))
+            self._segmentVolume = np.pi / (self._inv[0] * self._inv[1] * u[2])
+        else:
+            self._inv = tuple(u[d] / L[d] for d in range(3))
+            self._segmentVolume = L[0] * L[1] * L[2] / (u[0] * u[1] * u[2])
+        self._uIDs = u[0] * u[1] * u[2]
+        self._engine = None
+
+    def quantities(self) -> int:
+        """the LS1HIP_PROF_* mask of the enabled profiles"""
+        E = DeviceEngine
+        return ((E.PROF_VELOCITY if self._velAbs else 0) | (E.PROF_VELOCITY3D if self._vel3d else 0) |
+                (E.PROF_TEMPERATURE if self._dofkin else 0) | (E.PROF_VIRIAL if self._virial else 0))
+
+    def component(self) -> int:
+        """0-based component id of ls1hip_profile_config (-1: all): componentid() == _profiledComp - 1 (SpatialProfile.cpp:244)"""
+        return -1 if self._profiledComp is None else self._profiledComp - 1
+
+    def attach(self, engine: DeviceEngine):
+        """configure the device tables of `engine` for this plugin instance (one instance per engine)"""
+        engine.profile_config(self.CYLINDER if self._cylinder else self.CARTESIAN, self._units, self.quantities(), self.component())
+        self._engine = engine
+
+    def samplesAt(self, simstep: int) -> bool:
+        return simstep >= self._initStatistics and simstep % self._profileRecordingTimesteps == 0
+
+    def writesAt(self, simstep: int) -> bool:
+        return simstep >= self._initStatistics and simstep % self._writeFrequency == 0
+
+    # --- SpatialProfile::endStep, SpatialProfile.cpp:233-328.  temperature: Domain::getCurrentTemperature(0) of this step, the value
+    # from the kinetic sums BEFORE the thermostat scales (Domain.cpp:204-240; a row of ls1hip_run_log gives it).  sample = False:
+    # the device loop has sampled already (ls1hip_run with profile_every / profile_from).
+    def endStep(self, simstep: int, temperature: float, domainDecomp=None, directory: str = ".", sample: bool = True):
+        if sample and self.samplesAt(simstep):
+            self._engine.profile_sample()
+        if self.writesAt(simstep):
+            collect = getattr(domainDecomp, "profile_collect", None)
+            tables = collect(self._engine) if collect else self._engine.profile_read()
+            rank = domainDecomp.getRank() if hasattr(domainDecomp, "getRank") else 0
+            if rank == 0:
+                self.write(tables, simstep, temperature, directory)
+            self._engine.profile_reset()
+
+    def write(self, tables, simstep: int, temperature: float, directory: str = "."):
+        import os
+
+        for suffix, text in self.render(tables, simstep, temperature).items():
+            with open(os.path.join(directory, "%s_%d%s" % (self._outputPrefix, simstep, suffix)), "w") as fh:
+                fh.write(text)
+
+    def render(self, tables, simstep: int, temperature: float):
+        """{file suffix: text} of every writer, from global tables as DeviceEngine.profile_read / decomp.profile_collect return them"""
+        acc = int(tables["samples"])
+        out = {}
+        if self._dens:
+            out[".NDpr"] = self._file("the number density", "DensityProfile", ["//local density profile: Y - Z || X-projection\n"], tables, acc,
+                                      lambda t, uID: [_div(float(t["n"][uID]), self._segmentVolume * acc)])
+        if self._velAbs:
+            out[".VAbspr"] = self._file("magnitude of velocity", "VelocityAbsProfile", ["//local velocity magnitude profile: Y - Z || X-projection\n"],
+                                        tables, acc, lambda t, uID: [_div(t["vabs"][uID], int(t["n"][uID])) if int(t["n"][uID]) != 0 else 0.0])
+        if self._vel3d:
+            out[".V3Dpr"] = self._file("X-Y-Z components of velocity", "Velocity3dProfile",
+                                       ["//local velocity component profile: Y - Z || X-projection\n"], tables, acc,
+                                       lambda t, uID: [_div(t["v3"][uID][d], int(t["n"][uID])) if int(t["n"][uID]) != 0 else 0.0 for d in range(3)])
+        if self._virial:
+            out["_1D-Y.Vipr"] = self._virial_file(tables, acc, temperature)
+        if self._temp:
+            out[".Temppr"] = self._file("the temperature", "TemperatureProfile",
+                                        ["//Temperature expressed by 2Ekin/#DOF\n", "//local temperature profile: Y - Z || X-projection\n"], tables, acc,
+                                        lambda t, uID: [_div(t["ekin"][uID], int(t["dof"][uID])) if int(t["dof"][uID]) != 0 else 0.0])
+        return out
+
+    def _head(self, what, method, acc):
+        local = "Local profile of " + what
+        return ["//Segment volume: ", _g6(self._segmentVolume), "\n//Accumulated data sets: ", str(acc), "\n//", local,
+                ". Output file generated by the \"", method, "\" method, plugins/profiles. \n"]
+
+    def _dxyz(self):
+        return ["// \t dX \t dY \t dZ \n", "\t", _g6(1 / self._inv[0]), "\t", _g6(1 / self._inv[1]), "\t", _g6(1 / self._inv[2]), "\n"]
+
+    # --- <Profile>::output + ProfileBase::writeMatrix (DensityProfile.cpp:7-37, ProfileBase.cpp:8-73)
+    def _file(self, what, method, lines, tables, acc, entry):
+        out = self._head(what, method, acc) + lines + self._dxyz() + ["0 \t"]
+        u, inv = self._units, self._inv
+        if self._cylinder:  # ProfileBase::writeCylMatrix
+            for r in range(u[0]):
+                out += [_g6(0.5 * (np.sqrt(r + 1) + np.sqrt(r)) / np.sqrt(inv[0])), " \t"]
+            out.append("\n")
+            for h in range(u[1]):
+                out += [_g6((h + 0.5) / inv[1]), "  \t"]
+                for phi in range(u[2]):
+                    for r in range(u[0]):
+                        for x in entry(tables, h * u[0] * u[2] + r * u[2] + phi):
+                            out += [_g6(x), "\t"]
+                out.append("\n")
+        else:  # ProfileBase::writeKartMatrix
+            for z in range(u[2]):
+                out += [_g6((z + 0.5) / inv[2]), "  \t"]
+            out.append("\n")
+            for y in range(u[1]):
+                out += [_g6((y + 0.5) / inv[1]), "  \t"]
+                for z in range(u[2]):
+                    for x in range(u[0]):
+                        for e in entry(tables, x * u[1] * u[2] + y * u[2] + z):
+                            out += [_g6(e), "\t"]
+                out.append("\n")
+        return "".join(out)
+
+    # --- VirialProfile::output (VirialProfile.cpp:7-96): the layer sums over the planes of constant y / h
+    def _virial_file(self, tables, acc, globalTemperature):
+        out = self._head("the partial pressures", "VirialProfile", acc) + self._dxyz() + ["0 \t\n", "# y\tvn-vt\tpx\tpy\tpz\n# \n"]
+        u, L = self._units, self._globalLength
+        layerHeight = L[1] / u[1]
+        if self._cylinder:
+            radius = L[0] / 2
+            layerVolume = layerHeight * np.pi * radius * radius
+        else:
+            layerVolume = layerHeight * L[0] * L[2]
+        ld = np.longdouble
+        vi, n = tables["vi3"], tables["n"]
+        for y in range(u[1]):
+            hval = (y + 0.5) / self._inv[1]
+            Px = Py = Pz = Ny = ld(0.0)
+            for a in range(u[0]):
+                for b in range(u[2]):
+                    unID = y * u[0] * u[2] + a * u[2] + b if self._cylinder else a * u[1] * u[2] + y * u[2] + b
+                    Px += ld(vi[unID][0])
+                    Py += ld(vi[unID][1])
+                    Pz += ld(vi[unID][2])
+                    Ny += ld(int(n[unID]))
+            Pd = Py - ld(.5) * (Px + Pz)
+            with np.errstate(all="ignore"):
+                den = ld(layerVolume * acc)
+                T = ld(globalTemperature)
+                out += [_g6(hval), "\t", _g6(Pd / den), "\t", _g6((T * Ny + Px) / den), "\t", _g6((T * Ny + Py) / den), "\t",
+                        _g6((T * Ny + Pz) / den), "\n"]
+        return "".join(out)
+
+
 class LinkedCells:
     """Device-resident replacement of the reference's LinkedCells (seam B of SURVEY.md 8b).
 
