@@ -421,6 +421,50 @@ int ls1hip_profile_reset(ls1hip_ctx* ctx);
  * velocities the reference's endStep sees — without touching the state.  A sampling step takes the loop's unfused route (as the
  * last step of a call does); per-step loops keep their trajectory bit for bit, list loops may move a rebuild. */
 
+/* ---- planar long-range correction ------------------------------------------------------------------------------------
+ * The reference's correction for vapour-liquid interfaces and films, longRange/Planar.{h,cpp} with _smooth = false: a density
+ * profile along y per LJ site and per dipolar component (a component with dipoles or charges), from it per-slab tables of force,
+ * energy and normal / tangential virial (centerCenter, centerSite, siteSite, dipoleDipole), applied to every site in every step.
+ * Rows: the LJ sites in component order (numLJSum2), then one row per dipolar component (numDipoleSum2).  The device keeps u64
+ * COUNTS per (row, slab) of the OWNED molecules — exact, reproducible, additive over ranks — and forms rho = count slabs / V
+ * when the tables are built; the slab sum is a gather in a fixed order, so equal counts give bit-equal tables.  Kept from the
+ * reference: pi = 3.1416, (int) truncation of y / delta with its one-slab wrap, the self terms as Planar.cpp:495-497, 556-560,
+ * 618-622, 805-809 write them, cutoff_slabs as a double, slabs / 2 as integer division, muSquare indexed by component id.
+ * DEVIATIONS: a centre whose y / delta rounds to `slabs` is counted in the last slab; LS1HIP_EINVAL for component sets in which a
+ * component without dipole / charge precedes one with (the reference reads outside muSquare there); the right-half self term of
+ * centerCenter is dropped where its row index (Planar.cpp:556) lies beyond the LJ rows (the reference writes outside its arrays).
+ * Not served: _smooth = true, the DistControl-tracked region, a fused-epilogue form. */
+/* Planar::readXML + init (Planar.cpp:40-218): slabs (0: off, buffers freed), frequency (density and tables are recomputed on
+ * every frequency-th call), the region [left, right] in y in which the FORCE is applied (u and the virial always are),
+ * temperature = the target temperature dipoleDipole uses (only read for dipolar components).  The cutoff is the LJ cutoff of the
+ * context.  Needs components and domain; restarts the call counter. */
+int ls1hip_planar_config(ls1hip_ctx* ctx, int slabs, int frequency, double region_left, double region_right, double temperature);
+/* One Planar::calculateLongRange() (Planar.cpp:220-476) of a single-rank domain, called where Simulation.cpp:841, 1048-1049 call it:
+ * after a force pass, before the forces are used.  Counts calls as the reference counts simsteps: density + tables when
+ * counter % frequency == 0 (so with the first call), then the tables are applied: F_y of every LJ site (inside the region), its
+ * torque in M, u and 2 vT + vN into the two results (Domain::setUpotCorr / setVirialCorr), (vT, vN, vT) into Vi with option
+ * compute_vi.  Needs valid forces; refused after a fused force + integration pass.  Timers "planar_density", "planar_tables",
+ * "planar_apply". */
+int ls1hip_long_range_planar(ls1hip_ctx* ctx, double* upot_corr, double* virial_corr);
+/* The same piecewise, for multi-rank hosts: _density ADDS the counts of this rank's owned molecules to whatever the device holds (the
+ * loop Planar.cpp:281-308) — the host must write ZEROS (_counts_write) before every sampling, or the previous global sum is counted
+ * again —, _counts_read / _counts_write move the [rows][slabs] u64 counts for the host's all-reduce (which replaces
+ * collCommAllreduceSum :320-336) and put the global sum on the device, _tables builds all tables from the counts
+ * now on the device — every rank the whole table, so the reference's second all-reduce (:374-400) disappears —, _apply is the
+ * molecule loop :404-460 and returns this rank's share of Upot_c / Virial_c (the operands of :463-469). */
+int ls1hip_planar_density(ls1hip_ctx* ctx);
+int ls1hip_planar_counts_read(ls1hip_ctx* ctx, size_t cap, uint64_t* counts);
+int ls1hip_planar_counts_write(ls1hip_ctx* ctx, size_t n, const uint64_t* counts);
+int ls1hip_planar_tables(ls1hip_ctx* ctx);
+int ls1hip_planar_apply(ls1hip_ctx* ctx, double* upot_corr, double* virial_corr);
+/* layout = {slabs, LJ rows, dipole rows} (zeros when off; may be NULL); rho, u, vN, vT, f: [LJ rows + dipole rows][slabs], the LJ
+ * rows first (rho_l, uLJ, vNLJ, vTLJ, fLJ | rhoDipoleL, uDipole, vNDipole, vTDipole, fDipole); any pointer may be NULL. */
+int ls1hip_planar_read(ls1hip_ctx* ctx, int layout[3], size_t cap, double* rho, double* u, double* vN, double* vT, double* f);
+/* Inside ls1hip_run a configured correction is called after every force pass; fused passes and the list pass's own kick are off
+ * (every step goes the unfused route of NVT steps).  {Upot_c, Virial_c} of every step go to a device ring beside the step log;
+ * rows2 [nrows][2], oldest first, as ls1hip_run_log. */
+int ls1hip_planar_log(ls1hip_ctx* ctx, size_t cap_rows, double* rows2, size_t* nrows);
+
 /* ---- multi-GPU plumbing: packed buffers a host transport (RCCL via torch.distributed, MPI, ...) moves ---------
  * Wire formats (little endian, FP64): leaving molecule = 15 doubles {id(as bits), cid(as bits), r3, v3, q4, D3}
  * (the reference's 116-byte record, parallel/CommunicationBuffer.cpp:131-145, padded to 120); halo molecule =

@@ -80,6 +80,15 @@ SYMBOLS = {
     "ls1hip_profile_sample": (C.c_int, [C.c_void_p]),
     "ls1hip_profile_read": (C.c_int, [C.c_void_p, C.c_size_t, _u64p, _u64p, _dp, _dp, _dp, _dp, _u64p]),
     "ls1hip_profile_reset": (C.c_int, [C.c_void_p]),
+    "ls1hip_planar_config": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "ls1hip_long_range_planar": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "ls1hip_planar_density": (C.c_int, [C.c_void_p]),
+    "ls1hip_planar_counts_read": (C.c_int, [C.c_void_p, C.c_size_t, _u64p]),
+    "ls1hip_planar_counts_write": (C.c_int, [C.c_void_p, C.c_size_t, _u64p]),
+    "ls1hip_planar_tables": (C.c_int, [C.c_void_p]),
+    "ls1hip_planar_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "ls1hip_planar_read": (C.c_int, [C.c_void_p, _ip, C.c_size_t, _dp, _dp, _dp, _dp, _dp]),
+    "ls1hip_planar_log": (C.c_int, [C.c_void_p, C.c_size_t, _dp, C.POINTER(C.c_size_t)]),
     "ls1hip_export_counts": (C.c_int, [C.c_void_p, C.c_int, _u64p]),
     "ls1hip_export_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "ls1hip_export_pack_dirs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t]),

@@ -63,6 +63,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	dfree(c->d_steplog);
 	rdf_destroy(c);
 	profile_destroy(c);
+	planar_destroy(c);
 	if (c->d_ingest) hipFree(c->d_ingest);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_flag) hipHostFree((void*)c->h_flag);
@@ -872,6 +873,9 @@ static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
 	if (n == "halo") return &c->t_halo;
 	if (n == "rdf") return &c->t_rdf;
 	if (n == "profile") return &c->t_profile;
+	if (n == "planar_density") return &c->t_pl_density;
+	if (n == "planar_tables") return &c->t_pl_tables;
+	if (n == "planar_apply") return &c->t_pl_apply;
 	return nullptr;
 }
 
@@ -888,7 +892,8 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
-	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile}) {
+	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile, &c->t_pl_density, &c->t_pl_tables,
+					 &c->t_pl_apply}) {
 		timer_collect(*t);
 		t->total_ms = 0;
 		t->launches = 0;

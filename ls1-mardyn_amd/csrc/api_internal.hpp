@@ -148,3 +148,7 @@ LS1_INTERNAL void rdf_destroy(ls1hip_ctx* c);
 // multiplied by the thermostat factors on the device
 LS1_INTERNAL int profile_sample_impl(ls1hip_ctx* c, bool scaled);
 LS1_INTERNAL void profile_destroy(ls1hip_ctx* c);
+// api_planar.hip: one Planar::calculateLongRange (ls1hip_long_range_planar; ls1hip_run with the correction configured); log2: ring
+// row that also receives {Upot_c, Virial_c}
+LS1_INTERNAL int planar_impl(ls1hip_ctx* c, double* log2);
+LS1_INTERNAL void planar_destroy(ls1hip_ctx* c);

@@ -977,11 +977,14 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	HIPCHK(c, hipSetDevice(c->device));
 	// Between two steps of an NVE run on the LJ fast path the force pass does the integration itself (fused mode, the
 	// reference's reduced-memory scheme); the last step is unfused so that F and the kinetic sums are available.
-	const bool fuse = c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
+	// With the planar long-range correction configured every step goes the unfused route NVT and sampling steps take: a force pass that
+	// leaves F, then Planar::calculateLongRange (Simulation.cpp:1048-1049: before the forces are used), then the kicks.
+	const bool planar = c->pl.slabs > 0;
+	const bool fuse = !planar && c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
 	// neighbour-list loop (fused or not: NVT and unfused NVE steps advance the displacement bound in their kick + drift pass)
 	const bool verlet = can_verlet(c) && can_list(c);
 	// the single-centre list pass does the post-force kick (+ sum m v^2) itself; the multi-site one leaves it to the integrator passes
-	const bool list_kick = verlet && (c->one_clj || (can_list_ms(c) && can_list_kick_ms(c)));
+	const bool list_kick = !planar && verlet && (c->one_clj || (can_list_ms(c) && can_list_kick_ms(c)));
 	bool advanced = false;  // the previous force pass already did kick + kick + drift
 	bool kicked = false;    // the previous step sampled profiles: its post-force kick (+ kinetic sums, betas) is done
 	// step log: one row {U_pot, virial, sum m v^2, sum I w^2, N, rotDOF} per step, written by the reductions on the device
@@ -1059,6 +1062,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			rc = advanced ? ls1hip_forces_kick_drift(c, 0, dt, nullptr, nullptr) : ls1hip_forces(c, 0, nullptr, nullptr);
 		}
 		if (rc) return rc;
+		if (planar && (rc = planar_impl(c, c->d_pl_log + (s % STEPLOG_ROWS) * 2))) return rc;
 		if (s + 1 == nsteps || prof_now) {
 			c->log_row_kin = c->log_row;
 			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;

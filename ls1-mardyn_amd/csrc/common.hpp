@@ -252,6 +252,37 @@ struct ProfParams {
 	unsigned long long* tab;  // global table (plain device memory)
 };
 
+// planar long-range correction (kernels_planar.hip): longRange/Planar.cpp
+constexpr int PL_CC = 0, PL_CS = 1, PL_SS = 2, PL_DD = 3;  // centerCenter, centerSite, siteSite, dipoleDipole
+struct PlanarPair {  // one ORDERED row pair (ci si, cj sj) of Planar::calculateLongRange (:338-371)
+	int kind, self_row;  // PL_*; row the right-half self term of centerCenter lands on (:556), -1: outside the tables
+	double sig, eps, t1, t2;  // PL_DD: sig = muSquare[ci] muSquare[cj] / (3 T), the rest unused
+};
+struct PlanarParams {
+	int slabs, nlj, ndip, nrows;  // nrows = nlj + ndip: LJ rows first, then one row per dipolar component
+	int half, nd;                 // slabs / 2 (integer division), distances tabulated: slabs - half
+	double delta, delta_inv, cutoff, cutoff_slabs, rho_unit;  // ymax / slabs, its inverse, r_c, r_c slabs / ymax, slabs / V
+	double len_y, region[2];
+	int ljrow[MAXC], drow[MAXC];  // first LJ row of a component (numLJSum2), its dipole row (numDipoleSum2) or -1
+	int with_vi, ncomp;
+	const double *x, *y, *z, *q0, *q1, *q2, *q3;
+	const int32_t* cid;
+	double *Fy, *Mx, *Mz, *Vix, *Viy, *Viz;
+	const CompTable* ct;
+	const DevCounters* cnt;
+	unsigned long long* counts;  // [nrows][slabs]
+	const PlanarPair* pairs;     // [nlj * nlj] then [ndip * ndip]
+	double* K;                   // [pair][4: u f vN vT][nd + 1], index = slab distance (0: the self term)
+	double* tab;                 // [4: u f vN vT][nrows][slabs]
+	double* partials;            // apply pass: [workgroups][2]
+	double *out2, *log2;         // {Upot_c, Virial_c} of the last apply pass; ring row of ls1hip_run (or null)
+};
+void launch_planar_clear(const PlanarParams& p, hipStream_t s);
+void launch_planar_density(const PlanarParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+void launch_planar_tables(const PlanarParams& p, hipStream_t s);
+uint32_t planar_apply_blocks(uint32_t n_cap);
+void launch_planar_apply(const PlanarParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+
 struct Timer {
 	std::vector<hipEvent_t> ev;  // start/stop pairs
 	size_t used = 0;
@@ -400,6 +431,17 @@ struct ls1hip_ctx {
 	// a fused force + integration pass wrote the velocities last: they are half a step ahead of the positions' force evaluation
 	bool half_advanced = false;
 	ls1::Timer t_profile;
+	// planar long-range correction (ls1hip_planar_*; kernels_planar.hip)
+	ls1::PlanarParams pl{};  // layout of the current configuration (slabs = 0: off)
+	long pl_frequency = 10;
+	unsigned long pl_calls = 0;  // simstep of Planar::calculateLongRange
+	bool pl_tables_valid = false;
+	unsigned long long* d_pl_counts = nullptr;
+	ls1::PlanarPair* d_pl_pairs = nullptr;
+	double *d_pl_K = nullptr, *d_pl_tab = nullptr, *d_pl_partials = nullptr, *d_pl_out = nullptr;
+	size_t pl_partials_cap = 0;
+	double* d_pl_log = nullptr;  // ring {Upot_c, Virial_c} beside the step log
+	ls1::Timer t_pl_density, t_pl_tables, t_pl_apply;
 	// streaming upload (ls1hip_upload_begin / _chunk / _records / _end)
 	bool ingest_open = false;
 	size_t ingest_total = 0, ingest_at = 0;

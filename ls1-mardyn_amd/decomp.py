@@ -501,6 +501,26 @@ def profile_collect(engine, dist=None, group=None, device=None):
     return out
 
 
+def planar_collect(engine, dist=None, group=None, device=None):
+    """The collective of Planar::calculateLongRange (longRange/Planar.cpp:320-336) on the device's u64 counts: ONE all-reduce, after
+    which every rank holds the global counts on its device and builds the whole table itself (ls1hip_planar_tables) — the
+    reference's second all-reduce (:374-400) has nothing left to sum.  Call after engine.planar_density(); returns the global counts.
+    The global sum stays on the device: before the NEXT engine.planar_density() write zeros (engine.planar_counts(np.zeros_like(c))),
+    since the density pass adds to what is there.  Without an initialised process group: the local counts."""
+    local = engine.planar_counts()
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    t = torch.from_numpy(local.astype(np.int64))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    return engine.planar_counts(t.cpu().numpy().astype(np.uint64))
+
+
 def build_strong_scaling_box(comps, rc, n_per_dim, world, rank, local_rank, rho, temp, cic=None, kernel=0,
                              stage_through_host=False, loopback=False, options=None, skin=None):
     """bench.py helper: the GLOBAL jittered bcc liquid of 2*n^3 molecules (synth.py) split over the rank grid; every

@@ -405,6 +405,65 @@ class DeviceEngine:
     def profile_reset(self):
         self._chk(self.lib.ls1hip_profile_reset(self.ctx))
 
+    # -- planar long-range correction (ls1hip_planar_*: the reference's longRange/Planar) ----------------------------------------
+    def planar_config(self, slabs: int, frequency: int = 10, region=None, temperature: float = 0.0):
+        """slabs = 0 switches the correction off; region = (left, right) in y where the force is applied (default: everywhere);
+        temperature: the target temperature dipoleDipole divides by."""
+        left, right = (-np.inf, np.inf) if region is None else region
+        self._chk(self.lib.ls1hip_planar_config(self.ctx, int(slabs), int(frequency), float(left), float(right), float(temperature)))
+
+    def planar(self):
+        """One Planar::calculateLongRange on the current forces; returns (Upot_c, Virial_c)."""
+        u = C.c_double(); w = C.c_double()
+        self._chk(self.lib.ls1hip_long_range_planar(self.ctx, C.byref(u), C.byref(w)))
+        return u.value, w.value
+
+    def planar_layout(self):
+        lay = (C.c_int * 3)()
+        self._chk(self.lib.ls1hip_planar_read(self.ctx, lay, 0, None, None, None, None, None))
+        return tuple(lay)  # slabs, LJ rows, dipole rows
+
+    def planar_density(self):
+        self._chk(self.lib.ls1hip_planar_density(self.ctx))
+
+    def planar_counts(self, counts=None):
+        """LOCAL u64 counts [rows, slabs] (LJ rows, then dipole rows); with `counts` given, writes them to the device instead."""
+        slabs, nlj, nd = self.planar_layout()
+        if counts is None:
+            out = np.zeros((nlj + nd, slabs), dtype=np.uint64)
+            self._chk(self.lib.ls1hip_planar_counts_read(self.ctx, out.size, out.ctypes.data_as(capi._u64p)))
+            return out
+        a = np.ascontiguousarray(counts, dtype=np.uint64)
+        self._chk(self.lib.ls1hip_planar_counts_write(self.ctx, a.size, a.ctypes.data_as(capi._u64p)))
+        return a
+
+    def planar_tables(self):
+        self._chk(self.lib.ls1hip_planar_tables(self.ctx))
+
+    def planar_apply(self):
+        u = C.c_double(); w = C.c_double()
+        self._chk(self.lib.ls1hip_planar_apply(self.ctx, C.byref(u), C.byref(w)))
+        return u.value, w.value
+
+    def planar_read(self):
+        """The tables: rho, u, vN, vT, f [LJ rows, slabs] and rho_d, u_d, vN_d, vT_d, f_d [dipole rows, slabs]."""
+        slabs, nlj, nd = self.planar_layout()
+        t = {k: np.zeros((nlj + nd, slabs)) for k in ("rho", "u", "vN", "vT", "f")}
+        self._chk(self.lib.ls1hip_planar_read(self.ctx, None, (nlj + nd) * slabs, *[capi.dptr(t[k]) for k in ("rho", "u", "vN", "vT", "f")]))
+        out = dict(slabs=slabs, nlj=nlj, ndip=nd)
+        for k, a in t.items():
+            out[k], out[k + "_d"] = a[:nlj], a[nlj:]
+        return out
+
+    def planar_log(self):
+        """[nsteps, 2] {Upot_c, Virial_c} of every step of the last run."""
+        n = C.c_size_t()
+        self._chk(self.lib.ls1hip_planar_log(self.ctx, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 2))
+        if n.value:
+            self._chk(self.lib.ls1hip_planar_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
+        return out
+
     # -- multi-GPU plumbing -----------------------------------------------------------------------------------------
     def export_counts(self, kind: int):
         c = np.zeros(27, dtype=np.uint64)

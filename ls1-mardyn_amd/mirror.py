@@ -17,6 +17,8 @@ Mirrored interfaces (reference file:line):
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from .engine import DeviceEngine
@@ -358,6 +360,60 @@ def _g6(x) -> str:
     if np.isinf(x):
         return "-inf" if x < 0 else "inf"
     return "%.6g" % x
+
+
+class Planar:
+    """The reference's planar long-range correction (longRange/Planar.{h,cpp}) over the device tables: readXML-style arguments
+    (slabs, frequency, region = (left, right) with right = "box" allowed, writecontrol start / frequency / stop), calculateLongRange
+    = one ls1hip_long_range_planar, writeProfiles = the LRC_TS%09d.dat writer (Planar.cpp:1110-1162)."""
+
+    def __init__(self, length, slabs: int = 10, frequency: int = 10, region=None, temperature: float = 0.0, start: int = 1,
+                 writefrequency: int = 10, stop: int = 100):
+        if writefrequency < 1 or stop <= start:
+            raise ValueError("writecontrol: frequency >= 1 and stop > start (Planar.cpp:196-205)")
+        self._ymax = float(np.asarray(length, dtype=np.float64)[1])
+        left, right = (0.0, self._ymax) if region is None else region
+        self._region = (float(left), self._ymax if right == "box" else float(right))
+        self._slabs, self._frequency, self._temperature = int(slabs), int(frequency), float(temperature)
+        self._write = (int(start), int(writefrequency), int(stop))
+        self._engine = None
+
+    def init(self, engine):
+        engine.planar_config(self._slabs, self._frequency, self._region, self._temperature)
+        self._engine = engine
+
+    def calculateLongRange(self, domain=None):
+        up, vir = self._engine.planar()
+        if domain is not None and hasattr(domain, "setUpotCorr"):
+            domain.setUpotCorr(up)
+            domain.setVirialCorr(vir)
+        return up, vir
+
+    def render(self, tables) -> str:
+        """the text of one file from tables as DeviceEngine.planar_read returns them (rho, f, u: [LJ rows, slabs])"""
+        rho, f, u = (np.asarray(tables[k], dtype=np.float64) for k in ("rho", "f", "u"))
+        rows, slabs = rho.shape
+        sci = lambda x: "%24s" % ("%.15e" % x)  # noqa: E731  FORMAT_SCI_MAX_DIGITS
+        out = ["                     pos"] + ["            rho_l_LRC[%d]                F_LRC[%d]                u_LRC[%d]" % (k, k, k) for k in range(rows)] + ["\n"]
+        per = self._ymax / slabs
+        for pi in range(slabs):
+            pos = per * (pi + 0.5)
+            # (the first position is written before any FORMAT_SCI_MAX_DIGITS: default notation; the flags stay set afterwards)
+            out.append("%24s" % _g6(pos) if pi == 0 else sci(pos))
+            inside = self._region[0] <= pos <= self._region[1]
+            for k in range(rows):
+                out += [sci(rho[k, pi]), sci(f[k, pi] if inside else 0.0), sci(u[k, pi])]
+            out.append("\n")
+        return "".join(out)
+
+    def writeProfiles(self, simstep: int, directory: str = ".", tables=None):
+        start, freq, stop = self._write
+        if simstep % freq != 0 or simstep < start or simstep > stop:
+            return None
+        path = os.path.join(directory, "LRC_TS%09d.dat" % simstep)
+        with open(path, "w") as fh:
+            fh.write(self.render(self._engine.planar_read() if tables is None else tables))
+        return path
 
 
 class SpatialProfile:
