@@ -465,6 +465,47 @@ int ls1hip_planar_read(ls1hip_ctx* ctx, int layout[3], size_t cap, double* rho, 
  * rows2 [nrows][2], oldest first, as ls1hip_run_log. */
 int ls1hip_planar_log(ls1hip_ctx* ctx, size_t cap_rows, double* rows2, size_t* nrows);
 
+/* ---- test-particle insertions, Widom sampling -----------------------------------------------------------------
+ * The energy a molecule WOULD have at a point, without adding it: what ChemicalPotential::grandcanonicalStep
+ * (ensemble/ChemicalPotential.cpp:451-591) asks LinkedCells::getEnergy for, once per ghost molecule
+ * (particleContainer/LinkedCells.cpp:998-1052 -> LegacyCellProcessor::processSingleMolecule, adapter/LegacyCellProcessor.cpp:34-54):
+ * dU = U6 / 6 + U_xpoles + U_RF of FluidPot (molecules/potforce.h:506-650, ParticlePairs2PotForceAdapter.h:170-176) over the
+ * molecules and halo copies whose centre lies inside r_c, with the parameter products, shift6, LJ cutoff on the centre distance
+ * and reaction-field term of the force kernels.  No long-range correction is added (the host may add 2 U_corr / N).
+ * DEVIATION: a partner whose centre coincides with the test's (dd == 0) is skipped, the mask of every force path here
+ * (VectorizedCellProcessor); the legacy processor would evaluate it.
+ * State: that of ls1hip_rdf_sample — molecules binned (or neighbour lists alive on a single-rank domain: the stale binning of
+ * the last build is complete, a partner inside r_c now was inside r_c + skin / 2 of the point then), halo valid, no split force
+ * pass in flight; the current positions are used wherever the engine keeps them.  cells_in_cutoff 1 and 2.  Nothing is written
+ * to the state.  Timer "insert". */
+/* n tests from HOST arrays: cid[n], r[n][3] inside this rank's [box_min, box_max), q[n][4] (normalised where the rotation is
+ * formed; NULL only if no test's component rotates), exclude_id[n] or NULL: id of a molecule the test does not see, with its
+ * periodic images (LegacyCellProcessor.cpp:44) — the energy of an EXISTING molecule is the call at its position with its id.
+ * dU[n]; exactly 0 where no partner is in range.  One wave per test, no atomics: the same state gives the same bits.
+ * LS1HIP_EINVAL names the first test with a component id out of range, a position outside the box or a missing q.  n = 0: OK. */
+int ls1hip_insertion_energies(ls1hip_ctx* ctx, size_t n, const int32_t* cid, const double* r, const double* q,
+							  const uint64_t* exclude_id, double* dU);
+/* Widom's method (the accumulation Domain::submitDU was meant for, Domain.cpp:810-829, its body commented out in the reference):
+ * every sample inserts `instances` ghost molecules of `component` at positions uniform in [cv_min, cv_max) (NULL, NULL: this
+ * rank's box; otherwise inside it) and adds w = exp(-dU / temperature) to slab floor(y / L_y * slabs) of the GLOBAL box.
+ * Test k of sample s is a pure function of (seed, s, k): counter-based, independent of the launch shape.  DEVIATION: a component
+ * with rotational degrees of freedom gets a uniformly distributed orientation; the reference inserts its reservoir molecule's
+ * fixed one (ChemicalPotential.cpp:393-402), which does not sample the ideal-gas orientation distribution.
+ * instances = 0: off, buffers freed.  Sums and sample counter start at zero. */
+int ls1hip_widom_config(ls1hip_ctx* ctx, int component, uint32_t instances, double temperature, uint64_t seed, int slabs,
+						const double cv_min[3], const double cv_max[3]);
+/* One sample on the current state (sample index = samples since the last reset). */
+int ls1hip_widom_sample(ls1hip_ctx* ctx);
+/* LOCAL sums of this rank, additive over ranks and samples: sum_w[slabs] (f64, accumulated with atomics: the last bits depend
+ * on the order), n[slabs] tests per slab; any pointer may be NULL. */
+int ls1hip_widom_read(ls1hip_ctx* ctx, size_t cap_slabs, double* sum_w, uint64_t* n, uint64_t* samples);
+/* The tests of the LAST sample: r[n][3], q[n][4], dU[n]; *n = their number (0 before the first sample); any pointer may be NULL. */
+int ls1hip_widom_last(ls1hip_ctx* ctx, size_t cap, double* r, double* q, double* dU, size_t* n);
+/* Sums, counts and the sample counter (hence the sample index) back to zero. */
+int ls1hip_widom_reset(ls1hip_ctx* ctx);
+/* Option "widom_every" (default 0 = never): ls1hip_run samples on every step s with s % widom_every == 0, at the place and with
+ * the step counting of "rdf_every"; an error without a configuration.  The pass only reads: the trajectory keeps its bits. */
+
 /* ---- multi-GPU plumbing: packed buffers a host transport (RCCL via torch.distributed, MPI, ...) moves ---------
  * Wire formats (little endian, FP64): leaving molecule = 15 doubles {id(as bits), cid(as bits), r3, v3, q4, D3}
  * (the reference's 116-byte record, parallel/CommunicationBuffer.cpp:131-145, padded to 120); halo molecule =
@@ -507,7 +548,7 @@ int ls1hip_soa_forces(ls1hip_ctx* ctx, const int cell_dims[3], const uint32_t* c
 /* Device time (ms, HIP events on the context's compute stream) and launch count accumulated per kernel class
  * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction),
  * "rdf" (RDF sampling pass),
- * "profile" (profile sampling pass)}. */
+ * "profile" (profile sampling pass), "insert" (insertion-energy pass)}. */
 int ls1hip_timing(ls1hip_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int ls1hip_timing_reset(ls1hip_ctx* ctx);
 /* Per-launch HIP-event timing: 0 = off, 1 = every phase, 2 = force passes only (each timed scope puts two event markers

@@ -64,6 +64,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	rdf_destroy(c);
 	profile_destroy(c);
 	planar_destroy(c);
+	insert_destroy(c);
 	if (c->d_ingest) hipFree(c->d_ingest);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_flag) hipHostFree((void*)c->h_flag);
@@ -130,6 +131,9 @@ extern "C" int ls1hip_set_option(ls1hip_ctx* c, const char* name, long v) {
 	} else if (n == "profile_every") {
 		REQUIRE(c, v >= 0, "profile_every must be >= 0 (0: ls1hip_run does not sample)");
 		c->opt_profile_every = v;
+	} else if (n == "widom_every") {
+		REQUIRE(c, v >= 0, "widom_every must be >= 0 (0: ls1hip_run does not sample)");
+		c->opt_widom_every = v;
 	} else if (n == "profile_from") {
 		REQUIRE(c, v >= 0, "profile_from must be >= 0");
 		c->opt_profile_from = v;
@@ -158,6 +162,7 @@ extern "C" int ls1hip_get_option(const ls1hip_ctx* c, const char* name, long* v)
 	else if (n == "rdf_every") *v = c->opt_rdf_every;
 	else if (n == "profile_every") *v = c->opt_profile_every;
 	else if (n == "profile_from") *v = c->opt_profile_from;
+	else if (n == "widom_every") *v = c->opt_widom_every;
 	else if (n == "verlet_irregular_bricks") {
 		// bricks of the last list build that do NOT run the production path of the list force pass (region beyond the LDS staging
 		// area, list overflow, more owned molecules than the tiles cover): read back from the device on request, any precision
@@ -873,6 +878,7 @@ static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
 	if (n == "halo") return &c->t_halo;
 	if (n == "rdf") return &c->t_rdf;
 	if (n == "profile") return &c->t_profile;
+	if (n == "insert") return &c->t_insert;
 	if (n == "planar_density") return &c->t_pl_density;
 	if (n == "planar_tables") return &c->t_pl_tables;
 	if (n == "planar_apply") return &c->t_pl_apply;
@@ -892,7 +898,7 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
-	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile, &c->t_pl_density, &c->t_pl_tables,
+	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile, &c->t_insert, &c->t_pl_density, &c->t_pl_tables,
 					 &c->t_pl_apply}) {
 		timer_collect(*t);
 		t->total_ms = 0;

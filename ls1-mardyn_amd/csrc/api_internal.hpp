@@ -1,4 +1,4 @@
-// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling; api_profile.hip: spatial profiles;
+// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling; api_profile.hip: spatial profiles; api_insert.hip: test-particle insertions, Widom sampling;
 // api_step.hip: the pieces of a time step, neighbour lists, ls1hip_run; api_exchange.hip: long-range correction, export / import of
 // the multi-rank exchange, seam A).  Round 4: split out of one 2 400-line api.hip; nothing here is exported from the
 // library (LS1_INTERNAL = hidden visibility).
@@ -152,3 +152,6 @@ LS1_INTERNAL void profile_destroy(ls1hip_ctx* c);
 // row that also receives {Upot_c, Virial_c}
 LS1_INTERNAL int planar_impl(ls1hip_ctx* c, double* log2);
 LS1_INTERNAL void planar_destroy(ls1hip_ctx* c);
+// api_insert.hip: one Widom sample (ls1hip_widom_sample; ls1hip_run with "widom_every")
+LS1_INTERNAL int widom_sample_impl(ls1hip_ctx* c);
+LS1_INTERNAL void insert_destroy(ls1hip_ctx* c);

@@ -283,6 +283,38 @@ void launch_planar_tables(const PlanarParams& p, hipStream_t s);
 uint32_t planar_apply_blocks(uint32_t n_cap);
 void launch_planar_apply(const PlanarParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
 
+// test-particle insertions (kernels_insert.hip): ChemicalPotential::grandcanonicalStep -> LinkedCells::getEnergy
+struct InsertParams {
+	Grid g;
+	const double *x, *y, *z, *q0, *q1, *q2, *q3;  // current positions / orientations, owned + halo segment
+	const int32_t* cid;
+	const uint64_t* id;
+	const uint32_t *cell_begin, *cell_end;
+	const uint32_t* hsrc;  // per halo slot: owned index of its source molecule (0xffffffff: imported record)
+	const CompTable* ct;
+	const DevCounters* cnt;
+	uint32_t n;              // tests
+	const int32_t* tcid;     // [n] component per test, or null: every test is of component `comp`
+	int comp;
+	const double *tr, *tq;   // [n][3] positions, [n][4] quaternions (null: identity)
+	const uint64_t* excl;    // [n] id of the molecule a test does not see, or null
+	double* dU;              // [n]
+	double eps24, sig2, shift6;  // single-centre LJ sets
+};
+struct WidomParams {
+	uint32_t n;
+	int slabs, rotates;  // rotates: the inserted component has rotational degrees of freedom
+	uint64_t seed, sample;
+	double lo[3], hi[3], len_y, temperature;
+	double *r, *q, *dU;         // [n][3], [n][4], [n]: the tests of the last sample
+	double* sum_w;              // [slabs]
+	unsigned long long* count;  // [slabs]
+};
+// mode 0: single-centre LJ set, 1: LJ-only set, 2: any set
+void launch_insert(const InsertParams& p, int mode, bool has_rot, hipStream_t s);
+void launch_widom_generate(const WidomParams& w, hipStream_t s);
+void launch_widom_accumulate(const WidomParams& w, hipStream_t s);
+
 struct Timer {
 	std::vector<hipEvent_t> ev;  // start/stop pairs
 	size_t used = 0;
@@ -442,6 +474,16 @@ struct ls1hip_ctx {
 	size_t pl_partials_cap = 0;
 	double* d_pl_log = nullptr;  // ring {Upot_c, Virial_c} beside the step log
 	ls1::Timer t_pl_density, t_pl_tables, t_pl_apply;
+	// test-particle insertions (ls1hip_insertion_energies, ls1hip_widom_*; kernels_insert.hip)
+	char* d_ins = nullptr;  // staging of ls1hip_insertion_energies: {r, q, dU, exclude_id, cid} of ins_cap tests
+	size_t ins_cap = 0;
+	ls1::WidomParams wd{};  // current Widom configuration (n = 0: off); r, q, dU, sum_w, count live in d_widom
+	int wd_comp = 0;
+	double* d_widom = nullptr;
+	uint64_t wd_samples = 0;
+	uint32_t wd_last = 0;   // tests of the last sample (0 before the first)
+	long opt_widom_every = 0;
+	ls1::Timer t_insert;
 	// streaming upload (ls1hip_upload_begin / _chunk / _records / _end)
 	bool ingest_open = false;
 	size_t ingest_total = 0, ingest_at = 0;

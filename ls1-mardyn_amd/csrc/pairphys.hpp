@@ -205,4 +205,65 @@ LS1_HD void dipole_quadrupole(V3 dr, double dr2, V3 ea, V3 eb, double dq15, V3& 
 	mb = (-dUdb_over_r) * cross(eb, dr) + dUdg * ea_x_eb;
 }
 
+// ---- energy-only forms of the seven bodies (molpair_energy.hpp: test-particle insertions need no force and no torque).  Every
+// energy is formed by the expressions of the force form above, in the same order, so it carries the same bits.
+LS1_HD double lj_u6(double dr2, double eps24, double sig2) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	double lj6 = sig2 * ir2;
+	lj6 = lj6 * lj6 * lj6;
+	const double lj12 = lj6 * lj6;
+	return eps24 * (lj12 - lj6);
+}
+LS1_HD double charge_charge_u(double dr2, double q1q2) {
+	const double ir1 = LS1_PAIR_SQRT(LS1_PAIR_RCP(dr2));
+	return q1q2 * ir1;
+}
+LS1_HD double charge_dipole_u(V3 dr, double dr2, V3 e, double neg_q_my) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	const double ir1 = LS1_PAIR_SQRT(ir2);
+	const double cb = dot(e, dr) * ir1;
+	return (neg_q_my * ir2) * cb;
+}
+LS1_HD double charge_quadrupole_u(V3 dr, double dr2, V3 e, double half_qQ) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	const double ir1 = LS1_PAIR_SQRT(ir2);
+	const double cb = dot(e, dr) * ir1;
+	const double w_cq = half_qQ * ir1 * ir2;
+	return w_cq * (3.0 * cb * cb - 1);
+}
+LS1_HD double dipole_dipole_u(V3 dr, double dr2, V3 ei, V3 ej, double my2, double rffac, double& rf) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	const double ir1 = LS1_PAIR_SQRT(ir2);
+	const double w_dd = my2 * ir2 * ir1;
+	double ca = dot(ei, dr), cb = dot(ej, dr);
+	const double cg = dot(ei, ej);
+	ca *= ir1;
+	cb *= ir1;
+	rf = -rffac * cg;
+	return w_dd * (cg - 3. * ca * cb);
+}
+LS1_HD double quadrupole_quadrupole_u(V3 dr, double dr2, V3 ei, V3 ej, double qq075) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	const double ir1 = LS1_PAIR_SQRT(ir2);
+	const double w_qq = qq075 * ir2 * ir2 * ir1;
+	double ca = dot(ei, dr), cb = dot(ej, dr);
+	const double cg = dot(ei, ej);
+	ca *= ir1;
+	cb *= ir1;
+	const double ca2 = ca * ca, cb2 = cb * cb;
+	const double term = (cg - 5. * ca * cb);
+	return w_qq * (1. - 5. * (ca2 + cb2) - 15. * ca2 * cb2 + 2. * term * term);
+}
+LS1_HD double dipole_quadrupole_u(V3 dr, double dr2, V3 ea, V3 eb, double dq15) {
+	const double ir2 = LS1_PAIR_RCP(dr2);
+	const double ir1 = LS1_PAIR_SQRT(ir2);
+	const double w_dq = dq15 * ir2 * ir2;
+	double ca = dot(ea, dr), cb = dot(eb, dr);
+	const double cg = dot(ea, eb);
+	ca *= ir1;
+	cb *= ir1;
+	const double cb2 = cb * cb;
+	return w_dq * (-ca * (5. * cb2 - 1.) + 2. * cg * cb);
+}
+
 }  // namespace ls1

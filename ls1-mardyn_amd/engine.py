@@ -26,6 +26,7 @@ class DeviceEngine:
         self.has_rot = False
         self.n_sites = []
         self.rdf_bins = 0
+        self.widom_slabs = 0
 
     # -- lifetime ---------------------------------------------------------------------------------------------------
     def close(self):
@@ -85,6 +86,7 @@ class DeviceEngine:
         if neighbor_rank is None:
             neighbor_rank = np.full(27, my_rank if periodic else -1, dtype=np.int32)
             neighbor_rank[13] = my_rank
+        self.global_len = gl.copy()
         nb = np.ascontiguousarray(neighbor_rank, dtype=np.int32)
         self._chk(self.lib.ls1hip_set_domain(self.ctx, capi.dptr(gl), capi.dptr(bmin), capi.dptr(bmax), int(my_rank),
                                              capi.iptr(nb)))
@@ -463,6 +465,51 @@ class DeviceEngine:
         if n.value:
             self._chk(self.lib.ls1hip_planar_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
         return out
+
+    # -- test-particle insertions, Widom sampling (ls1hip_insertion_energies, ls1hip_widom_*) -------------------------------------
+    def insertion_energies(self, cid, r, q=None, exclude_id=None):
+        """dU [n] of n test molecules (component cid[n], centre r[n, 3] inside the box, quaternion q[n, 4]) in the current state;
+        exclude_id[n]: id of a molecule a test does not see (the energy of an existing molecule: its position, its id)."""
+        n = len(cid)
+        cid = np.ascontiguousarray(cid, dtype=np.int32)
+        r = capi.f64(r, (n, 3))
+        q = capi.f64(q, (n, 4)) if q is not None else None
+        ex = np.ascontiguousarray(exclude_id, dtype=np.uint64) if exclude_id is not None else None
+        dU = np.zeros(n)
+        self._chk(self.lib.ls1hip_insertion_energies(self.ctx, n, cid.ctypes.data_as(capi._i32p), capi.dptr(r), capi.dptr(q),
+                                                     ex.ctypes.data_as(capi._u64p) if ex is not None else None, capi.dptr(dU)))
+        return dU
+
+    def widom_config(self, component: int, instances: int, temperature: float, seed: int = 0, slabs: int = 1, cv_min=None, cv_max=None):
+        """instances = 0 switches the sampling off and frees the device buffers; cv_min / cv_max: control volume (default: the box)."""
+        lo = capi.f64(cv_min, (3,)) if cv_min is not None else None
+        hi = capi.f64(cv_max, (3,)) if cv_max is not None else None
+        self._chk(self.lib.ls1hip_widom_config(self.ctx, int(component), int(instances), float(temperature), int(seed), int(slabs),
+                                               capi.dptr(lo), capi.dptr(hi)))
+        self.widom_slabs = int(slabs) if instances else 0
+
+    def widom_sample(self):
+        """One sample of `instances` test insertions on the current state (the state rules of rdf_sample)."""
+        self._chk(self.lib.ls1hip_widom_sample(self.ctx))
+
+    def widom_read(self):
+        """LOCAL sums of this rank: sum_w [slabs] of exp(-dU / T), n uint64 [slabs] tests per slab, samples."""
+        s = self.widom_slabs
+        sw = np.zeros(s); n = np.zeros(s, dtype=np.uint64); smp = C.c_uint64()
+        self._chk(self.lib.ls1hip_widom_read(self.ctx, s, capi.dptr(sw), n.ctypes.data_as(capi._u64p), C.byref(smp)))
+        return dict(sum_w=sw, n=n, samples=int(smp.value))
+
+    def widom_last(self):
+        """The tests of the last sample: r [n, 3], q [n, 4], dU [n]."""
+        n = C.c_size_t()
+        self._chk(self.lib.ls1hip_widom_last(self.ctx, 0, None, None, None, C.byref(n)))
+        r = np.zeros((n.value, 3)); q = np.zeros((n.value, 4)); dU = np.zeros(n.value)
+        if n.value:
+            self._chk(self.lib.ls1hip_widom_last(self.ctx, n.value, capi.dptr(r), capi.dptr(q), capi.dptr(dU), C.byref(n)))
+        return dict(r=r, q=q, dU=dU)
+
+    def widom_reset(self):
+        self._chk(self.lib.ls1hip_widom_reset(self.ctx))
 
     # -- multi-GPU plumbing -----------------------------------------------------------------------------------------
     def export_counts(self, kind: int):

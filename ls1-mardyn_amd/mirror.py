@@ -596,6 +596,55 @@ class SpatialProfile:
         return "".join(out)
 
 
+class Widom:
+    """Residual chemical potential from test insertions on the device (ls1hip_widom_*): per slab of the y axis
+    mu_res = -T ln(sum_w / n), sum_w the accumulated exp(-dU / T) of the n tests that fell into the slab.
+
+    Multi-rank: every rank samples its own box; the per-rank sum_w and n are ADDITIVE — sum them over the ranks (and over
+    runs) and pass the sums to mu_res / render.  Orientations of rotating components are uniformly distributed, unlike the
+    reference's fixed reservoir orientation."""
+
+    def __init__(self, engine, component: int, instances: int, T: float, seed: int, slabs: int = 1, cv_min=None, cv_max=None,
+                 length_y: float | None = None):
+        self.engine, self.T, self.slabs = engine, float(T), int(slabs)
+        self.length_y = float(engine.global_len[1] if length_y is None else length_y)
+        engine.widom_config(component, instances, T, seed, slabs, cv_min, cv_max)
+
+    def sample(self):
+        self.engine.widom_sample()
+
+    @staticmethod
+    def mu_res_of(sum_w, n, T):
+        """(total, per slab) of -T ln(sum_w / n); nan where n = 0, +inf where every test overlapped."""
+        sum_w, n = np.asarray(sum_w, dtype=np.float64), np.asarray(n, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per = np.where(n > 0, -T * np.log(sum_w / n), np.nan)
+            tot = -T * np.log(sum_w.sum() / n.sum()) if n.sum() > 0 else float("nan")
+        return float(tot), per
+
+    def mu_res(self):
+        t = self.engine.widom_read()
+        return self.mu_res_of(t["sum_w"], t["n"], self.T)
+
+    @staticmethod
+    def render(sum_w, n, T, length_y):
+        """The table of write(): `# slab y_mid n <w> mu_res`, one line per slab, then `# total n <w> mu_res`."""
+        sum_w, n = np.asarray(sum_w, dtype=np.float64), np.asarray(n, dtype=np.uint64)
+        tot, per = Widom.mu_res_of(sum_w, n, T)
+        out = ["# slab\ty_mid\tn\t<w>\tmu_res\n"]
+        for k in range(len(n)):
+            w = sum_w[k] / float(n[k]) if n[k] else float("nan")
+            out.append("%d\t%.10g\t%d\t%.12e\t%.12e\n" % (k, (k + 0.5) * length_y / len(n), int(n[k]), w, per[k]))
+        nt = int(n.sum())
+        out.append("# total\t%d\t%.12e\t%.12e\n" % (nt, sum_w.sum() / nt if nt else float("nan"), tot))
+        return "".join(out)
+
+    def write(self, path):
+        t = self.engine.widom_read()
+        with open(path, "w") as fh:
+            fh.write(self.render(t["sum_w"], t["n"], self.T, self.length_y))
+
+
 class LinkedCells:
     """Device-resident replacement of the reference's LinkedCells (seam B of SURVEY.md 8b).
 
