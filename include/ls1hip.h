@@ -506,6 +506,67 @@ int ls1hip_widom_reset(ls1hip_ctx* ctx);
 /* Option "widom_every" (default 0 = never): ls1hip_run samples on every step s with s % widom_every == 0, at the place and with
  * the step counting of "rdf_every"; an error without a configuration.  The pass only reads: the trajectory keeps its bits. */
 
+/* ---- region-wise temperature control (slab thermostat) -----------------------------------------------------------------------
+ * Replaces: thermostats/TemperatureControl.{h,cpp}, method VelocityScaling, as Simulation.cpp:1137-1140 calls it (after the
+ * post-force kick and Domain::calculateGlobalValues).  Every control region is a cuboid cut into `numslabs` slabs along y; each
+ * slab has its own kinetic sums {n, rotDOF, ekinTrans = sum m v_d^2 over the masked directions, ekinRot = sum I w^2}, its own
+ *   betaTrans = pow(ndir n T / ekinTrans, exponent) (1 when n < 1), betaRot = pow(rotDOF T / ekinRot, exponent) (1 when rotDOF < 1)
+ * (TemperatureControl.cpp:283-301) and scales the masked velocity components by 2 - 1 / betaTrans and D by 2 - 1 / betaRot
+ * (:392-409).  A molecule takes part when it is STRICTLY inside the region (:316-320, 371-375) with the component filter passed
+ * (:311-313); its slab is (unsigned) floor((y - lc_y) / width), ignored beyond numslabs - 1 (:329-333).  Positions are those of
+ * the current force evaluation, wrapped into the global box (in list mode molecules sit up to skin / 2 outside it); only owned
+ * molecules take part.  A step is a control step when simstep % frequency == 0 (:639, 645, 651); measurement and new betas happen
+ * only when also start <= simstep < stop (:719) — on a control step outside that window the scaling uses the betas of the LAST
+ * measurement (1 with count 0 before the first).  All regions measure before any region scales; regions scale in their order, a
+ * molecule inside two regions is scaled twice.
+ * Limits: at most 8 regions.  The measure sweep keeps the slab sums of all regions in LDS per workgroup up to 1024 slabs in total
+ * and adds to global memory directly above that; the apply passes stage the factors in LDS up to 256 slabs in total.  Counts are
+ * exact; the f64 slab sums are accumulated with atomics and may differ in the last bits from run to run.  Not served: the method
+ * Andersen, the addedEkin files, DistControl-tracked corners (refcoordsID).
+ * State rules: those of ls1hip_kick — velocities full-step (call after the post-force kick), positions valid, no split or fused
+ * pass in flight; nothing but v and D is written.  Excludes ls1hip_set_thermostat(enabled).  Timers "tempcontrol_measure",
+ * "tempcontrol_betas", "tempcontrol_apply". */
+#define LS1HIP_TC_X 1
+#define LS1HIP_TC_Y 2
+#define LS1HIP_TC_Z 4
+/* control/start, frequency, stop (TemperatureControl.cpp:579-586).  frequency = 0 removes the thermostat and its regions. */
+int ls1hip_tempcontrol_config(ls1hip_ctx* ctx, unsigned long start, unsigned long frequency, unsigned long stop);
+/* Appends a region (ControlRegionT::readXML + VelocityScalingInit, :90-236; AddRegion :636) and returns its 1-based id (> 0), or
+ * an error code (< 0).  component: 0 every component, else the 1-based id; direction_mask: LS1HIP_TC_X | _Y | _Z (the
+ * reference's x, y, z, xy, xz, yz, xyz).  Appending a region puts EVERY region back to the state before its first measurement. */
+int ls1hip_tempcontrol_region(ls1hip_ctx* ctx, const double lc[3], const double uc[3], double target_T, int component, unsigned numslabs,
+							  double exponent, unsigned direction_mask);
+/* _dTargetTemperature of one region; the temperature ramp (:266-277) stays on the host and calls this. */
+int ls1hip_tempcontrol_target(ls1hip_ctx* ctx, int region, double target_T);
+/* TemperatureControl::DoLoopsOverMolecules (:685-707) for step `simstep`: nothing on a step that is no control step. */
+int ls1hip_temperature_control(ls1hip_ctx* ctx, unsigned long simstep);
+/* The pieces, for hosts that reduce over ranks (the caller applies the window rule):
+ *   _measure      the molecule loop of VelocityScalingPreparation (:725-728): LOCAL sums ADDED to the table
+ *   _sums_read / _sums_write   the buffer of the all-reduce of CalcGlobalValues (:240-264): per slab of every region, regions in
+ *                 their order, 32 bytes {u64 n, u64 rotDOF, f64 ekinRot, f64 ekinTrans}
+ *   _betas        CalcGlobalValues after the all-reduce (:279-305): betas, factors, the sum-over-slabs accumulators, the sampled
+ *                 configuration counter; keeps the sums as those of the last measurement and zeroes the table
+ *   _apply        the molecule loop of DoLoopsOverMolecules (:700-703) with the factors of the last _betas
+ *   _apply_kick_drift   _apply followed by ls1hip_kick_drift(dt) in one pass: the same bits */
+int ls1hip_tempcontrol_measure(ls1hip_ctx* ctx);
+int ls1hip_tempcontrol_sums_read(ls1hip_ctx* ctx, size_t cap_slabs, void* sums);
+int ls1hip_tempcontrol_sums_write(ls1hip_ctx* ctx, size_t nslabs, const void* sums);
+int ls1hip_tempcontrol_betas(ls1hip_ctx* ctx);
+int ls1hip_tempcontrol_apply(ls1hip_ctx* ctx);
+int ls1hip_tempcontrol_apply_kick_drift(ls1hip_ctx* ctx, double dt);
+/* One region: the slab sums of the last measurement and its betas ([numslabs] each), beta_sums2 = {_dBetaTransSumGlobal,
+ * _dBetaRotSumGlobal} (sums over slabs AND measurements) with their configuration count — what WriteBetaLogfile reads (:455-488);
+ * reset != 0 puts the accumulators and the count back to zero as it does.  Any pointer may be NULL. */
+int ls1hip_tempcontrol_read(ls1hip_ctx* ctx, int region, size_t cap_slabs, uint64_t* n, uint64_t* rot_dof, double* ekin_trans, double* ekin_rot,
+							double* beta_trans, double* beta_rot, double* beta_sums2, uint64_t* configs, int reset);
+/* regions configured, their slab counts (slabs8[8]), and the two LDS limits above (slabs of all regions together). */
+int ls1hip_tempcontrol_layout(const ls1hip_ctx* ctx, int* regions, uint32_t* slabs8, size_t* lds_slabs, size_t* apply_lds_slabs);
+/* ls1hip_run with temperature control configured: every step goes the unfused route (as NVT steps do); simstep is the run's step
+ * counter, as for the profiles.  On a control step the measure sweep and the beta kernel follow the post-force kick; the scaling
+ * is folded into the next step's kick + drift, and is a standalone pass after the last step and before a profile sampling pass
+ * (SpatialProfile::endStep sees the scaled velocities).  The step log keeps the UNSCALED kinetic sums (calculateGlobalValues runs
+ * before the control).  Works together with the planar correction.  Without a configuration ls1hip_run is what it was. */
+
 /* ---- multi-GPU plumbing: packed buffers a host transport (RCCL via torch.distributed, MPI, ...) moves ---------
  * Wire formats (little endian, FP64): leaving molecule = 15 doubles {id(as bits), cid(as bits), r3, v3, q4, D3}
  * (the reference's 116-byte record, parallel/CommunicationBuffer.cpp:131-145, padded to 120); halo molecule =

@@ -95,6 +95,18 @@ SYMBOLS = {
     "ls1hip_widom_read": (C.c_int, [C.c_void_p, C.c_size_t, _dp, _u64p, _u64p]),
     "ls1hip_widom_last": (C.c_int, [C.c_void_p, C.c_size_t, _dp, _dp, _dp, C.POINTER(C.c_size_t)]),
     "ls1hip_widom_reset": (C.c_int, [C.c_void_p]),
+    "ls1hip_tempcontrol_config": (C.c_int, [C.c_void_p, C.c_ulong, C.c_ulong, C.c_ulong]),
+    "ls1hip_tempcontrol_region": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_int, C.c_uint, C.c_double, C.c_uint]),
+    "ls1hip_tempcontrol_target": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "ls1hip_temperature_control": (C.c_int, [C.c_void_p, C.c_ulong]),
+    "ls1hip_tempcontrol_measure": (C.c_int, [C.c_void_p]),
+    "ls1hip_tempcontrol_sums_read": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ls1hip_tempcontrol_sums_write": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ls1hip_tempcontrol_betas": (C.c_int, [C.c_void_p]),
+    "ls1hip_tempcontrol_apply": (C.c_int, [C.c_void_p]),
+    "ls1hip_tempcontrol_apply_kick_drift": (C.c_int, [C.c_void_p, C.c_double]),
+    "ls1hip_tempcontrol_read": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _u64p, _u64p, _dp, _dp, _dp, _dp, _dp, _u64p, C.c_int]),
+    "ls1hip_tempcontrol_layout": (C.c_int, [C.c_void_p, _ip, _u32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ls1hip_export_counts":(C.c_int, [C.c_void_p, C.c_int, _u64p]),
     "ls1hip_export_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "ls1hip_export_pack_dirs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t]),
@@ -112,6 +124,9 @@ HALO_DOUBLES = 9
 REFRESH_DOUBLES = 3
 FK_AUTO, FK_GENERIC, FK_LDS_LIST, FK_MS_BRICK, FK_MS_SITES, FK_NEIGHBOUR_LIST = 0, 1, 2, 3, 4, 5
 REC_ICRVQD, REC_ICRV, REC_IRV = 0, 1, 2
+TC_DIRECTIONS = {"x": 1, "y": 2, "z": 4, "xy": 3, "xz": 5, "yz": 6, "xyz": 7}  # settings/directions -> LS1HIP_TC_X | _Y | _Z
+# one slab of the all-reduce buffer of the temperature control (ls1hip_tempcontrol_sums_read / _write)
+TC_SUMS = np.dtype([("n", "<u8"), ("rotdof", "<u8"), ("ekin_rot", "<f8"), ("ekin_trans", "<f8")])
 REC_BYTES = {REC_ICRVQD: 116, REC_ICRV: 60, REC_IRV: 56}
 
 

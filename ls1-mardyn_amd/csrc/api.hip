@@ -65,6 +65,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	profile_destroy(c);
 	planar_destroy(c);
 	insert_destroy(c);
+	tempcontrol_destroy(c);
 	if (c->d_ingest) hipFree(c->d_ingest);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_flag) hipHostFree((void*)c->h_flag);
@@ -737,6 +738,7 @@ extern "C" int ls1hip_count(const ls1hip_ctx* c, size_t* n_owned, size_t* n_halo
 extern "C" int ls1hip_set_thermostat(ls1hip_ctx* c, int enabled, double target_temperature) {
 	if (!c) return LS1HIP_EINVAL;
 	REQUIRE(c, !enabled || target_temperature > 0., "target temperature must be positive");
+	REQUIRE(c, !enabled || c->tc_frequency == 0, "temperature control is configured (ls1hip_tempcontrol_config): the two thermostats exclude each other");
 	c->thermostat_on = enabled != 0;
 	c->thermostat_T = target_temperature;
 	return LS1HIP_OK;
@@ -882,6 +884,9 @@ static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
 	if (n == "planar_density") return &c->t_pl_density;
 	if (n == "planar_tables") return &c->t_pl_tables;
 	if (n == "planar_apply") return &c->t_pl_apply;
+	if (n == "tempcontrol_measure") return &c->t_tc_measure;
+	if (n == "tempcontrol_betas") return &c->t_tc_betas;
+	if (n == "tempcontrol_apply") return &c->t_tc_apply;
 	return nullptr;
 }
 
@@ -899,7 +904,7 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
 	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_profile, &c->t_insert, &c->t_pl_density, &c->t_pl_tables,
-					 &c->t_pl_apply}) {
+					 &c->t_pl_apply, &c->t_tc_measure, &c->t_tc_betas, &c->t_tc_apply}) {
 		timer_collect(*t);
 		t->total_ms = 0;
 		t->launches = 0;

@@ -155,3 +155,13 @@ LS1_INTERNAL void planar_destroy(ls1hip_ctx* c);
 // api_insert.hip: one Widom sample (ls1hip_widom_sample; ls1hip_run with "widom_every")
 LS1_INTERNAL int widom_sample_impl(ls1hip_ctx* c);
 LS1_INTERNAL void insert_destroy(ls1hip_ctx* c);
+// api_tempcontrol.hip: region-wise temperature control.  tempcontrol_params: the kernel arguments for the current state (positions of
+// the current force evaluation); tempcontrol_measure_impl: measure sweep + beta kernel when simstep lies in the control window
+// (VelocityScalingPreparation); tempcontrol_apply_impl: the standalone scaling pass
+LS1_INTERNAL TcParams tempcontrol_params(ls1hip_ctx* c);
+LS1_INTERNAL bool tempcontrol_is_control_step(const ls1hip_ctx* c, unsigned long simstep);
+LS1_INTERNAL int tempcontrol_measure_impl(ls1hip_ctx* c, unsigned long simstep);
+LS1_INTERNAL int tempcontrol_apply_impl(ls1hip_ctx* c);
+LS1_INTERNAL void tempcontrol_destroy(ls1hip_ctx* c);
+// api_step.hip: the scaling folded into the pre-force kick + drift (ls1hip_tempcontrol_apply_kick_drift; ls1hip_run)
+LS1_INTERNAL int tempcontrol_kick_drift_impl(ls1hip_ctx* c, double dt);

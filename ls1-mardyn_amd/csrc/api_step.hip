@@ -472,6 +472,36 @@ static int kick_drift_impl(ls1hip_ctx* c, double dt, int pre_scale, double bt, d
 	return LS1HIP_OK;
 }
 
+// ControlTemperature of every region (TemperatureControl.cpp:364-409) folded into the pre-force kick + drift of the next step: the
+// state rules and the bookkeeping of kick_drift_impl; the caller has checked the temperature-control state
+int tempcontrol_kick_drift_impl(ls1hip_ctx* c, double dt) {
+	REQUIRE(c, !c->pos_x || c->forces_valid, "positions were already advanced by ls1hip_forces_kick_drift (call ls1hip_rebin)");
+	if (c->pos_x && !c->vl_ready) {
+		int rcm = materialise_positions(c);
+		if (rcm) return rcm;
+	}
+	const TcParams P = tempcontrol_params(c);  // (regions and factor table: the pass reads the positions through IntegArgs)
+	TimedScope ts(c, c->t_integrate);
+	bool wrote_pk = false;
+	if (c->vl_ready) {
+		const IntegArgs a = integ_args_lists(c, dt);
+		launch_tc_kick_drift(a, P, c->stream);
+		wrote_pk = a.pk != nullptr;
+		// the per-brick drift-speed bounds of the force pass do not know the slabs' factors: the global bound decides alone
+		c->vl_top2_pending = false;
+		int rcb = track_unfused_drift(c, dt);
+		if (rcb) return rcb;
+	} else {
+		launch_tc_kick_drift(integ_args(c, dt), P, c->stream);
+	}
+	HIPCHK(c, hipGetLastError());
+	c->binned = false;
+	c->halo_valid = false;
+	c->forces_valid = false;
+	c->msl_pk_fresh = wrote_pk;
+	return LS1HIP_OK;
+}
+
 extern "C" int ls1hip_kick_then_kick_drift(ls1hip_ctx* c, double dt) {
 	if (!c) return LS1HIP_EINVAL;
 	REQUIRE(c, c->forces_valid, "forces are not valid (call ls1hip_forces)");
@@ -981,7 +1011,12 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	// With the planar long-range correction configured every step goes the unfused route NVT and sampling steps take: a force pass that
 	// leaves F, then Planar::calculateLongRange (Simulation.cpp:1048-1049: before the forces are used), then the kicks.
 	const bool planar = c->pl.slabs > 0;
-	const bool fuse = !planar && c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
+	// Region-wise temperature control (Simulation.cpp:1137-1140: after the post-force kick and calculateGlobalValues): every step goes
+	// the unfused route as well; on a control step the measure sweep and the beta kernel follow the post-force kick, the scaling is
+	// folded into the next step's kick + drift (standalone after the last step and before a profile sampling pass)
+	const bool tc = c->tc_frequency > 0 && c->tc.nreg > 0;
+	REQUIRE(c, !(tc && c->thermostat_on), "temperature control and the device thermostat exclude each other");
+	const bool fuse = !planar && !tc && c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
 	// neighbour-list loop (fused or not: NVT and unfused NVE steps advance the displacement bound in their kick + drift pass)
 	const bool verlet = can_verlet(c) && can_list(c);
 	// the single-centre list pass does the post-force kick (+ sum m v^2) itself; the multi-site one leaves it to the integrator passes
@@ -1014,6 +1049,15 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			// In list mode the force pass of step s-1 has done the post-force kick and the kinetic sum (betas on the device).
 			if (!list_kick && !kicked && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
 			if ((rc = kick_drift_impl(c, dt, 2, 1., 1.))) return rc;
+		} else if (tc && !kicked) {
+			// the post-force kick of step s-1 (+ kinetic sums: calculateGlobalValues sees the unscaled velocities), then
+			// DoLoopsOverMolecules of that step: measurement inside the control window, the scaling with the kick + drift
+			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
+			if (tempcontrol_is_control_step(c, c->run_step)) {
+				if ((rc = tempcontrol_measure_impl(c, c->run_step)) || (rc = tempcontrol_kick_drift_impl(c, dt))) return rc;
+			} else if ((rc = ls1hip_kick_drift(c, dt))) {
+				return rc;
+			}
 		} else if (list_kick || kicked) {
 			if ((rc = ls1hip_kick_drift(c, dt))) return rc;  // (post-force kick already done by the list force pass)
 		} else {
@@ -1074,6 +1118,10 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
 			// the thermostat's scaling waits for the next kick + drift pass (or the scale pass below): the sampling pass bins
 			// beta * v and beta * D with the factors the kick's reduction left on the device, the state stays as it is
+			// temperature control: the sampling pass (and whoever reads the state after the run) sees the scaled velocities — the
+			// standalone apply; the head of the next step then only kicks and drifts
+			if (tc && tempcontrol_is_control_step(c, simstep) && ((rc = tempcontrol_measure_impl(c, simstep)) || (rc = tempcontrol_apply_impl(c))))
+				return rc;
 			if (prof_now && (rc = profile_sample_impl(c, c->thermostat_on))) return rc;
 			kicked = s + 1 < nsteps;
 			if (s + 1 == nsteps && c->thermostat_on) {

@@ -315,6 +315,39 @@ void launch_insert(const InsertParams& p, int mode, bool has_rot, hipStream_t s)
 void launch_widom_generate(const WidomParams& w, hipStream_t s);
 void launch_widom_accumulate(const WidomParams& w, hipStream_t s);
 
+// region-wise temperature control (kernels_tempcontrol.hip): thermostats/TemperatureControl.{h,cpp}, method VelocityScaling
+constexpr int TC_MAXREG = 8;
+constexpr int TC_N = 0, TC_ROTDOF = 1, TC_EKIN_ROT = 2, TC_EKIN_TRANS = 3;  // words of a slab's sums (order of the reference's all-reduce)
+constexpr int TC_BETA_TRANS = 0, TC_BETA_ROT = 1, TC_VCORR = 2, TC_DCORR = 3;  // doubles of a slab's factors
+struct TcRegion {
+	double lc[3], uc[3], width, target_T, exponent;  // _dLowerCorner, _dUpperCorner, _dSlabWidth, _dTargetTemperature, _dTemperatureExponent
+	uint32_t slabs, off;  // _nNumSlabs; first slab of the region in the tables
+	int comp;             // _nTargetComponentID: 0 every component, else the 1-based component id
+	int dir[3], ndir;     // the Accumulator's flags, _nNumThermostatedTransDirections
+};
+struct TcParams {
+	int nreg, ncomp;
+	uint32_t total;  // slabs of all regions
+	TcRegion reg[TC_MAXREG];
+	double len[3];
+	const double *x, *y, *z, *q0, *q1, *q2, *q3;
+	double *vx, *vy, *vz, *Dx, *Dy, *Dz;
+	const int32_t* cid;
+	const CompTable* ct;
+	const DevCounters* cnt;
+	unsigned long long* sums;  // [total][4] {n, rotDOF (u64), ekinRot, ekinTrans (f64)}: the running measurement
+	unsigned long long* last;  // [total][4] the sums of the last completed measurement
+	double* fac;               // [total][4] {betaTrans, betaRot, vcorr, Dcorr}
+	double* acc;               // [nreg][2] sum over slabs and measurements of betaTrans, betaRot
+};
+size_t tempcontrol_lds_slabs();        // most slabs (all regions) whose sums a workgroup of the measure sweep keeps in LDS
+size_t tempcontrol_apply_lds_slabs();  // most slabs whose factors a workgroup of the apply passes stages in LDS
+void launch_tc_init(const TcParams& p, hipStream_t s);  // sums = 0, factors = 1
+void launch_tc_measure(const TcParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+void launch_tc_betas(const TcParams& p, hipStream_t s);
+void launch_tc_clear_acc(const TcParams& p, int region, hipStream_t s);
+void launch_tc_apply(const TcParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+
 struct Timer {
 	std::vector<hipEvent_t> ev;  // start/stop pairs
 	size_t used = 0;
@@ -484,6 +517,13 @@ struct ls1hip_ctx {
 	uint32_t wd_last = 0;   // tests of the last sample (0 before the first)
 	long opt_widom_every = 0;
 	ls1::Timer t_insert;
+	// region-wise temperature control (ls1hip_tempcontrol_*; kernels_tempcontrol.hip)
+	ls1::TcParams tc{};  // regions and table layout (nreg = 0: none); sums, last, fac, acc live in d_tc
+	unsigned long tc_start = 0, tc_frequency = 0, tc_stop = 0;  // control/start, frequency (0: not configured), stop
+	unsigned long long* d_tc = nullptr;
+	size_t tc_cap = 0;  // slabs d_tc has room for
+	uint64_t tc_configs[ls1::TC_MAXREG] = {0};  // _numSampledConfigs per region
+	ls1::Timer t_tc_measure, t_tc_betas, t_tc_apply;
 	// streaming upload (ls1hip_upload_begin / _chunk / _records / _end)
 	bool ingest_open = false;
 	size_t ingest_total = 0, ingest_at = 0;
@@ -679,5 +719,8 @@ void launch_kick_then_kick_drift(const IntegArgs& a, hipStream_t s);
 void launch_kin_reduce(DevCounters* cnt, const double* partials, uint32_t nblocks, hipStream_t s, double target_T,
 					   double* log = nullptr);
 void launch_scale(const IntegArgs& a, double beta_trans, double beta_rot, bool from_device, hipStream_t s);
+// kernels_tempcontrol.hip: the scaling of launch_tc_apply followed by the arithmetic of launch_kick_drift, one pass (a.pre_scale is
+// ignored; a.mol.x/y/z are the current positions: membership is decided before they move)
+void launch_tc_kick_drift(const IntegArgs& a, const TcParams& p, hipStream_t s);
 
 }  // namespace ls1

@@ -96,6 +96,49 @@ __device__ __forceinline__ double leap_post_pre(double dt, double mass, V3 invI,
 	return vx * vx + vy * vy + vz * vz;
 }
 
+// upd_preF alone (FullMolecule.cpp:334-364), operation for operation the body of k_kick_drift (kernels_integrate.hip) without its
+// pre-scaling: s holds full-step v and D -> v and D half a step on, position / orientation one step on.  Returns |v|^2 of the drift.
+// The body of the kick + drift pass that first applies the region-wise temperature control (kernels_tempcontrol.hip), which must
+// advance a molecule to the bits k_kick_drift gives.
+template <bool HAS_ROT>
+__device__ __forceinline__ double leap_pre(double dt, double mass, V3 invI, V3 F, V3 M, LeapState& s) {
+#pragma clang fp contract(off)
+	const double dt_halve = .5 * dt;
+	const double dtInv2m = dt_halve / mass;
+	double vx = s.vx, vy = s.vy, vz = s.vz;
+	vx += dtInv2m * F.x;
+	vy += dtInv2m * F.y;
+	vz += dtInv2m * F.z;
+	s.vx = vx;
+	s.vy = vy;
+	s.vz = vz;
+	s.x = s.x + dt * vx;
+	s.y = s.y + dt * vy;
+	s.z = s.z + dt * vz;
+	if (HAS_ROT) {
+		double* const q = s.q;
+		V3 D = s.D;
+		V3 w = rotate_inv(rot_of(q[0], q[1], q[2], q[3]), D);
+		w = {w.x * invI.x, w.y * invI.y, w.z * invI.z};
+		double dq[4], qh[4];
+		leap_q_diff(q, w, dq);
+		for (int k = 0; k < 4; ++k) qh[k] = dq[k] * dt_halve + q[k];
+		double qcorr = 1. / sqrt(qh[0] * qh[0] + qh[1] * qh[1] + qh[2] * qh[2] + qh[3] * qh[3]);
+		for (int k = 0; k < 4; ++k) qh[k] *= qcorr;
+		D.x += dt_halve * M.x;
+		D.y += dt_halve * M.y;
+		D.z += dt_halve * M.z;
+		w = rotate_inv(rot_of(qh[0], qh[1], qh[2], qh[3]), D);
+		w = {w.x * invI.x, w.y * invI.y, w.z * invI.z};
+		leap_q_diff(qh, w, dq);
+		for (int k = 0; k < 4; ++k) q[k] += dq[k] * dt;
+		qcorr = 1. / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+		for (int k = 0; k < 4; ++k) q[k] = q[k] * qcorr;
+		s.D = D;
+	}
+	return vx * vx + vy * vy + vz * vz;
+}
+
 // m v^2 and I w^2 of one molecule from its current velocity / angular momentum (Molecule::calculate_mv2_Iw2,
 // FullMolecule.cpp:398-404): the body of k_kin_by_component (kernels_integrate.hip) and of the profile sampling pass
 // (kernels_profile.hip), which must agree term by term.

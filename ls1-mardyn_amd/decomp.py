@@ -521,6 +521,28 @@ def planar_collect(engine, dist=None, group=None, device=None):
     return engine.planar_counts(t.cpu().numpy().astype(np.uint64))
 
 
+def tempcontrol_collect(engine, dist=None, group=None, device=None):
+    """The collective of ControlRegionT::CalcGlobalValues (thermostats/TemperatureControl.cpp:240-264) on the device's slab sums of
+    all regions: ONE all-reduce of a [4, slabs] float64 tensor {n, rotDOF, ekinRot, ekinTrans}.  Call between engine.tempcontrol_measure() and engine.tempcontrol_betas(); returns the global sums, which are then on the device.
+    Without an initialised process group: the local sums."""
+    local = engine.tempcontrol_sums()
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    # counts stay far below 2^53: exact as float64, so the four columns share one tensor and one all-reduce
+    t = torch.from_numpy(np.stack([local["n"].astype(np.float64), local["rotdof"].astype(np.float64), local["ekin_rot"], local["ekin_trans"]]))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    g = t.cpu().numpy()
+    out = np.zeros(len(local), dtype=local.dtype)
+    out["n"], out["rotdof"], out["ekin_rot"], out["ekin_trans"] = g[0].astype(np.uint64), g[1].astype(np.uint64), g[2], g[3]
+    return engine.tempcontrol_sums(out)
+
+
 def build_strong_scaling_box(comps, rc, n_per_dim, world, rank, local_rank, rho, temp, cic=None, kernel=0,
                              stage_through_host=False, loopback=False, options=None, skin=None):
     """bench.py helper: the GLOBAL jittered bcc liquid of 2*n^3 molecules (synth.py) split over the rank grid; every

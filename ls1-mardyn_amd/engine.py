@@ -466,6 +466,68 @@ class DeviceEngine:
             self._chk(self.lib.ls1hip_planar_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
         return out
 
+    # -- region-wise temperature control (ls1hip_tempcontrol_*: the reference's thermostats/TemperatureControl) --------------------
+    def tempcontrol_config(self, start: int, frequency: int, stop: int):
+        """control/start, frequency, stop; frequency = 0 removes the thermostat and its regions."""
+        self._chk(self.lib.ls1hip_tempcontrol_config(self.ctx, int(start), int(frequency), int(stop)))
+
+    def tempcontrol_region(self, lc, uc, target_T: float, component: int = 0, numslabs: int = 1, exponent: float = 0.4, directions="xyz") -> int:
+        """Appends a region and returns its 1-based id.  component: 0 all, else 1-based; directions: 'x' .. 'xyz' or the bit mask."""
+        mask = capi.TC_DIRECTIONS[directions] if isinstance(directions, str) else int(directions)
+        rid = self.lib.ls1hip_tempcontrol_region(self.ctx, capi.dptr(capi.f64(lc)), capi.dptr(capi.f64(uc)), float(target_T), int(component),
+                                                 int(numslabs), float(exponent), mask)
+        if rid <= 0:
+            self._chk(rid if rid else -1)
+        return rid
+
+    def tempcontrol_target(self, region: int, target_T: float):
+        self._chk(self.lib.ls1hip_tempcontrol_target(self.ctx, int(region), float(target_T)))
+
+    def temperature_control(self, simstep: int):
+        """TemperatureControl::DoLoopsOverMolecules of step `simstep` (after the post-force kick)."""
+        self._chk(self.lib.ls1hip_temperature_control(self.ctx, int(simstep)))
+
+    def tempcontrol_layout(self):
+        nreg, slabs, a, b = C.c_int(), (C.c_uint32 * 8)(), C.c_size_t(), C.c_size_t()
+        self._chk(self.lib.ls1hip_tempcontrol_layout(self.ctx, C.byref(nreg), slabs, C.byref(a), C.byref(b)))
+        return dict(slabs=list(slabs)[:nreg.value], lds_slabs=a.value, apply_lds_slabs=b.value)
+
+    def tempcontrol_measure(self):
+        self._chk(self.lib.ls1hip_tempcontrol_measure(self.ctx))
+
+    def tempcontrol_sums(self, sums=None):
+        """LOCAL slab sums of all regions (capi.TC_SUMS records, the reference's all-reduce layout); with `sums` given, writes them."""
+        total = sum(self.tempcontrol_layout()["slabs"])
+        if sums is None:
+            out = np.zeros(total, dtype=capi.TC_SUMS)
+            self._chk(self.lib.ls1hip_tempcontrol_sums_read(self.ctx, total, out.ctypes.data))
+            return out
+        a = np.ascontiguousarray(sums, dtype=capi.TC_SUMS)
+        self._chk(self.lib.ls1hip_tempcontrol_sums_write(self.ctx, a.size, a.ctypes.data))
+        return a
+
+    def tempcontrol_betas(self):
+        self._chk(self.lib.ls1hip_tempcontrol_betas(self.ctx))
+
+    def tempcontrol_apply(self):
+        self._chk(self.lib.ls1hip_tempcontrol_apply(self.ctx))
+
+    def tempcontrol_apply_kick_drift(self, dt: float):
+        """tempcontrol_apply() followed by kick_drift(dt), one pass, the same bits."""
+        self._chk(self.lib.ls1hip_tempcontrol_apply_kick_drift(self.ctx, float(dt)))
+
+    def tempcontrol_read(self, region: int, reset: bool = False):
+        """Slab sums of the last measurement, betas, and the beta accumulators {beta_trans_sum, beta_rot_sum, configs} of a region."""
+        ns = self.tempcontrol_layout()["slabs"][region - 1]
+        out = dict(n=np.zeros(ns, np.uint64), rotdof=np.zeros(ns, np.uint64), ekin_trans=np.zeros(ns), ekin_rot=np.zeros(ns),
+                   beta_trans=np.zeros(ns), beta_rot=np.zeros(ns))
+        acc, cfg = np.zeros(2), C.c_uint64()
+        self._chk(self.lib.ls1hip_tempcontrol_read(self.ctx, int(region), ns, out["n"].ctypes.data_as(capi._u64p), out["rotdof"].ctypes.data_as(capi._u64p),
+                                                   *[capi.dptr(out[k]) for k in ("ekin_trans", "ekin_rot", "beta_trans", "beta_rot")], capi.dptr(acc),
+                                                   C.byref(cfg), 1 if reset else 0))
+        out.update(beta_trans_sum=acc[0], beta_rot_sum=acc[1], configs=cfg.value)
+        return out
+
     # -- test-particle insertions, Widom sampling (ls1hip_insertion_energies, ls1hip_widom_*) -------------------------------------
     def insertion_energies(self, cid, r, q=None, exclude_id=None):
         """dU [n] of n test molecules (component cid[n], centre r[n, 3] inside the box, quaternion q[n, 4]) in the current state;

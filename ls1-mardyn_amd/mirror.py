@@ -416,6 +416,85 @@ class Planar:
         return path
 
 
+class TemperatureControl:
+    """The reference's region-wise thermostat (thermostats/TemperatureControl.{h,cpp}, method VelocityScaling) over the device passes:
+    readXML-style arguments (control start / frequency / stop; per region a dict with lc, uc ('box' allowed per coordinate),
+    temperature, component, numslabs, exponent, directions, writefreq, fileprefix and optionally ramp = dict(start, end, update_start,
+    update_stop, update_freq)), DoLoopsOverMolecules = one ls1hip_temperature_control, write = the beta_log writer.  Inside
+    ls1hip_run the device does the control itself; call ramp(simstep) / write(simstep) between runs."""
+
+    def __init__(self, length, start: int = 0, frequency: int = 1, stop: int = 2 ** 63 - 1, regions=()):
+        L = np.asarray(length, dtype=np.float64)
+        self._control = (int(start), int(frequency), int(stop))
+        self._regions = []
+        for r in regions:
+            uc = [L[d] if u == "box" else float(u) for d, u in enumerate(r["uc"])]
+            ramp = r.get("ramp")
+            if ramp:  # TemperatureControl.cpp:142-152
+                ramp = dict(ramp, elapsed=0, slope=(ramp["end"] - ramp["start"]) / (ramp["update_stop"] - ramp["update_start"]))
+            writefreq = int(r.get("writefreq", 1000)) or 1000  # 0 is reset to 1000 (:208-213)
+            self._regions.append(dict(lc=[float(x) for x in r["lc"]], uc=uc, temperature=float(r["temperature"]), component=int(r.get("component", 0)),
+                                      numslabs=int(r.get("numslabs", 1)), exponent=float(r.get("exponent", 0.0)), directions=r.get("directions", "xyz"),
+                                      writefreq=writefreq, fileprefix=r.get("fileprefix", "beta_log"), ramp=ramp))
+        self._engine = None
+
+    def _measures(self, simstep: int) -> bool:
+        start, freq, stop = self._control
+        return simstep % freq == 0 and start <= simstep < stop
+
+    def init(self, engine, directory: str | None = None):
+        """configure the device; with a directory also InitBetaLogfile (TemperatureControl.cpp:435-453): the 8-byte write frequency"""
+        engine.tempcontrol_config(*self._control)
+        for k, r in enumerate(self._regions):
+            rid = engine.tempcontrol_region(r["lc"], r["uc"], r["temperature"], r["component"], r["numslabs"], r["exponent"], r["directions"])
+            assert rid == k + 1
+            if directory is not None:
+                with open(os.path.join(directory, "%s_reg%d.dat" % (r["fileprefix"], rid)), "wb") as fh:
+                    fh.write(np.uint64(r["writefreq"]).tobytes())
+        self._engine = engine
+
+    def ramp(self, simstep: int):
+        """the target temperature adjustment of CalcGlobalValues (TemperatureControl.cpp:266-277), before the betas of `simstep`"""
+        if not self._measures(simstep):
+            return
+        for k, r in enumerate(self._regions):
+            m = r["ramp"]
+            if m and m["update_start"] < simstep <= m["update_stop"]:
+                if m["elapsed"] == 0:
+                    r["temperature"] = m["start"]
+                elif m["update_stop"] == simstep:
+                    r["temperature"] = m["end"]
+                elif m["elapsed"] % m["update_freq"] == 0:
+                    r["temperature"] = m["start"] + m["elapsed"] * m["slope"]
+                m["elapsed"] += 1
+                self._engine.tempcontrol_target(k + 1, r["temperature"])
+
+    def DoLoopsOverMolecules(self, simstep: int, directory: str | None = None):
+        self.ramp(simstep)
+        self._engine.temperature_control(simstep)
+        if directory is not None:
+            self.write(simstep, directory)
+
+    def write(self, simstep: int, directory: str = "."):
+        """WriteBetaLogfile (TemperatureControl.cpp:455-488) of every region: on a measuring step with simstep % writefreq == 0 two
+        doubles are appended — the sums over slabs AND configurations of betaTrans / betaRot divided by the number of configurations
+        (not by the slabs: the reference's quirk, kept) — and the accumulators start again."""
+        if not self._measures(simstep):
+            return []
+        paths = []
+        for k, r in enumerate(self._regions):
+            if simstep % r["writefreq"] != 0:
+                continue
+            t = self._engine.tempcontrol_read(k + 1, reset=True)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = np.float64(1.0) / np.float64(t["configs"])
+                rec = np.array([t["beta_trans_sum"] * inv, t["beta_rot_sum"] * inv], dtype="<f8")
+            paths.append(os.path.join(directory, "%s_reg%d.dat" % (r["fileprefix"], k + 1)))
+            with open(paths[-1], "ab") as fh:
+                fh.write(rec.tobytes())
+        return paths
+
+
 class SpatialProfile:
     """The reference's SpatialProfile plugin (plugins/SpatialProfile.{h,cpp}, plugins/profiles/*) over the device tables.
     Constructor arguments = the nodes SpatialProfile::readXML reads (SpatialProfile.cpp:22-134): mode ("cartesian" / "cylinder" or
