@@ -368,6 +368,41 @@ int ls1hip_rdf_reset(ls1hip_ctx* ctx);
  * positions of that step's force evaluation, directly before the force pass, on the step's regenerated or refreshed halo; the
  * trajectory does not change. */
 
+/* ---- orientation distribution functions ---------------------------------------------------------------------------
+ * The reference's ODF plugin (io/ODF.{h,cpp}) and its ODFCellProcessor (particleContainer/adapter/ODFCellProcessor.cpp): a
+ * traversal of the linked cells that histograms the mutual orientation of every pair of SINGLE-DIPOLE molecules (components with
+ * exactly one dipole, ODFCellProcessor.cpp:25,34; dipole direction (0, 0, 1) in the body frame, ODF.cpp:42-45) whose centres are
+ * closer than min(r_c, shellcutoff) (ODFCellProcessor.cpp:40, ODF.cpp:151).  Per pair, with d = r_j - r_i taken with the halo
+ * image of j and e_k = (2(qx qz + qw qy), 2(qy qz - qw qx), 1 - 2(qx^2 + qy^2)) of the quaternion as stored (ODF.cpp:191-193):
+ *   c1 = d^.e_i, c2 = -d^.e_j, cg = p^_i.p^_j with p_k = d^ x (e_k x d^) (ODF.cpp:197-229); each of the three is replaced by its
+ *   nearest integer when |c| < 1e-4 or ||c| - 1| < 1e-4 (:234-242); gamma = acos(cg);
+ *   i1: 1 - 2 i / P >= c1 > 1 - 2 (i + 1) / P, c1 == -1 -> P - 1; i2 likewise from c2; g = i + 1 with i pi / G <= gamma <
+ *   (i + 1) pi / G, gamma == pi -> G (:253-290); a value that fits nowhere (NaN: e parallel to d) keeps index 0.
+ * Layout (u64 words): four arrays of W = P P G + 1 words (ODF.cpp:51; word 0 is the reference's unused element) in the order
+ * 11 12 21 22; a pair with component ids (a, b) in {0, 1} adds 1 to H[a][b][i1 P G + i2 G + g] and to H[b][a][i2 P G + i1 G + g]
+ * (elementID, elementIDreversed, :305-329), so the sum does not depend on which molecule of a pair plays i.  Every unordered pair
+ * is counted once in the sum over all ranks (the rank that owns the smaller id counts it), also across periodic faces.
+ *
+ * ls1hip_odf_config: ODF::readXML + ODF::init (ODF.cpp:6-79) — phi1increments, phi2increments, gammaincrements, shellcutoff.
+ *   All increments 0: sampling off, buffers freed.  LS1HIP_EINVAL for phi1 != phi2 (the reference's reversed index, :306, is not
+ *   the transposed one there and can leave its array), shell_cutoff <= 0 or > r_c, a single-dipole component with id >= 2 (the
+ *   reference has the four arrays of the ids 0 and 1, :73-76), 4 W beyond the 32-bit word index.  Arrays start at zero. */
+int ls1hip_odf_config(ls1hip_ctx* ctx, int phi1_increments, int phi2_increments, int gamma_increments, double shell_cutoff);
+/* W of the current configuration (0 when off). */
+int ls1hip_odf_layout(const ls1hip_ctx* ctx, size_t* words_per_array);
+/* One traversal (ODF::afterForces -> traverseCells(ODFCellProcessor), ODF.cpp:81-85) of the CURRENT positions and orientations,
+ * added to the device arrays; the sample counter goes up by 1.  State: that of ls1hip_rdf_sample (binned, halo valid, no split
+ * pass in flight, cells_in_cutoff = 1).  Timer "odf". */
+int ls1hip_odf_sample(ls1hip_ctx* ctx);
+/* LOCAL counts of this rank (the inputs of ODF::collect, ODF.cpp:333-384), hist[4][W] in the order 11 12 21 22 (may be NULL);
+ * *samples = traversals since the last reset. */
+int ls1hip_odf_read(ls1hip_ctx* ctx, uint64_t* hist, size_t cap, uint64_t* samples);
+/* ODF::reset (ODF.cpp:104-121): arrays and sample counter back to zero. */
+int ls1hip_odf_reset(ls1hip_ctx* ctx);
+/* Options "odf_every" (_recordingTimesteps; default 0 = never) and "odf_from" (_initStatistics, default 0): ls1hip_run samples on
+ * every step s with s > odf_from && s % odf_every == 0 (ODF.cpp:82), s counted as for "rdf_every", at the place of the RDF pass;
+ * an error without a configuration.  Read-only option "odf_lds_words": the 4 W up to which a workgroup keeps the arrays in LDS. */
+
 /* ---- spatial profiles ----------------------------------------------------------------------------------------------
  * The reference's SpatialProfile plugin (plugins/SpatialProfile.{h,cpp}) with the profiles of plugins/profiles/: per bin of a
  * Cartesian or cylindrical sampling grid over the GLOBAL box the number of molecules and, on request, sums of |v|, v, 3 + rotDOF,
@@ -608,7 +643,7 @@ int ls1hip_soa_forces(ls1hip_ctx* ctx, const int cell_dims[3], const uint32_t* c
 
 /* Device time (ms, HIP events on the context's compute stream) and launch count accumulated per kernel class
  * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction),
- * "rdf" (RDF sampling pass),
+ * "rdf" (RDF sampling pass), "odf" (ODF sampling pass),
  * "profile" (profile sampling pass), "insert" (insertion-energy pass)}. */
 int ls1hip_timing(ls1hip_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int ls1hip_timing_reset(ls1hip_ctx* ctx);

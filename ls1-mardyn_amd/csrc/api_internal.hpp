@@ -144,6 +144,8 @@ LS1_INTERNAL void macro_to_upot_virial(const DevCounters* h, double* upot, doubl
 LS1_INTERNAL int materialise_positions(ls1hip_ctx* c);
 LS1_INTERNAL int rdf_sample_impl(ls1hip_ctx* c);  // api_rdf.hip: one RDF traversal (ls1hip_rdf_sample; ls1hip_run with "rdf_every")
 LS1_INTERNAL void rdf_destroy(ls1hip_ctx* c);
+LS1_INTERNAL int odf_sample_impl(ls1hip_ctx* c);  // api_odf.hip: one ODF traversal (ls1hip_odf_sample; ls1hip_run with "odf_every")
+LS1_INTERNAL void odf_destroy(ls1hip_ctx* c);
 // api_profile.hip: one profile sampling pass (ls1hip_profile_sample; ls1hip_run with "profile_every"); scaled: bin the velocities
 // multiplied by the thermostat factors on the device
 LS1_INTERNAL int profile_sample_impl(ls1hip_ctx* c, bool scaled);

@@ -233,6 +233,18 @@ struct RdfParams {
 	unsigned long long *g_mol, *g_site, *g_n;  // global histograms, owned molecules per component
 };
 
+// orientation distribution functions (kernels_odf.hip): io/ODF.cpp:123-331, adapter/ODFCellProcessor.cpp
+struct OdfParams {
+	int P, G;           // phi1 = phi2 increments, gamma increments
+	uint32_t W;         // words per array: P P G + 1 (ODF.cpp:51), word 0 unused
+	double cut2;        // min(rc^2, shellcutoff^2) (ODFCellProcessor.cpp:40, ODF.cpp:151)
+	uint32_t dip_mask;  // bit c: component c has exactly one dipole (ODFCellProcessor.cpp:25,34); only bits 0 and 1 may be set
+	int hist_lds;       // the four arrays are kept in LDS per workgroup (else global atomics): the budget rule of launch_odf
+	const uint64_t* id;    // molecule ids, owned + halo segment
+	const uint32_t* hsrc;  // per halo slot: owned index of its source molecule (0xffffffff: imported record)
+	unsigned long long* g_hist;  // [4][W], arrays in the order 11 12 21 22
+};
+
 // spatial profiles (kernels_profile.hip): plugins/SpatialProfile.{h,cpp}, plugins/profiles/*
 struct ProfParams {
 	int mode;           // LS1HIP_PROF_CARTESIAN / LS1HIP_PROF_CYLINDER
@@ -485,6 +497,15 @@ struct ls1hip_ctx {
 	long opt_rdf_every = 0;
 	unsigned long run_step = 0;  // steps ls1hip_run has done on this context (simstep of RDF::afterForces)
 	ls1::Timer t_rdf;
+	// orientation distribution functions (ls1hip_odf_*; kernels_odf.hip): one device buffer of four arrays (11 12 21 22) of odf_words
+	int odf_phi = 0, odf_gamma = 0;  // phi1 = phi2 increments (0: off), gamma increments
+	double odf_shell = 0.;
+	uint32_t odf_mask = 0;  // single-dipole components at configuration time
+	unsigned long long* d_odf = nullptr;
+	size_t odf_words = 0;
+	uint64_t odf_samples = 0;
+	long opt_odf_every = 0, opt_odf_from = 0;
+	ls1::Timer t_odf;
 	// spatial profiles (ls1hip_profile_*; kernels_profile.hip): one device table, layout of ProfParams
 	int prof_mode = 0, prof_comp = -1;
 	unsigned prof_quant = 0;
@@ -663,6 +684,9 @@ bool launch_force_ms_list(const ForceParams& p, bool has_rot, bool lj_only, bool
 						  const double* shift27, double* pk, hipStream_t s, uint32_t* nblocks, size_t partials_cap, bool pk_fresh = false);
 // RDF sampling pass over all bricks (kernels_rdf.hip); fills r.mol_lds / r.site_lds; false: the grid cannot be served (hw != 1)
 bool launch_rdf(const ForceParams& p, RdfParams r, bool has_rot, double mean_per_cell, hipStream_t s);
+// ODF sampling pass over all bricks (kernels_odf.hip); fills o.hist_lds; false: the grid cannot be served (hw != 1)
+bool launch_odf(const ForceParams& p, OdfParams o, bool has_rot, double mean_per_cell, hipStream_t s);
+size_t odf_lds_words();  // most u32 words (4 W) a workgroup keeps in LDS (above it: global atomics)
 // spatial-profile sampling pass over the owned molecules (kernels_profile.hip); n_cap: launch bound (n_real is read on the device)
 void launch_profile(const ProfParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
 size_t profile_lds_words();  // largest table a workgroup keeps in LDS (above it: run-merged global atomics)

@@ -473,6 +473,24 @@ def rdf_collect(engine, dist=None, group=None, device=None):
     return out
 
 
+def odf_collect(engine, dist=None, group=None, device=None):
+    """ODF::collect (io/ODF.cpp:333-384): the four local arrays of every rank summed by ONE all-reduce (int64).  Returns the dict of
+    DeviceEngine.odf_read with global values; `samples` is this rank's own (every rank samples the same steps).  Without an
+    initialised process group: the local values."""
+    local = engine.odf_read()
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    t = torch.from_numpy(local["hist"].reshape(-1).astype(np.int64))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    return dict(local, hist=t.cpu().numpy().astype(np.uint64).reshape(local["hist"].shape))
+
+
 def profile_collect(engine, dist=None, group=None, device=None):
     """The collective of SpatialProfile::endStep (plugins/SpatialProfile.cpp:286-310): the local tables of every rank summed by
     at most two all-reduces — one int64 block {n, dof}, one float64 block {ekin, vabs, v3, vi3} (the reference appends one value per

@@ -362,6 +362,32 @@ class DeviceEngine:
     def rdf_reset(self):
         self._chk(self.lib.ls1hip_rdf_reset(self.ctx))
 
+    # -- orientation distribution functions (ls1hip_odf_*: the reference's ODF plugin + ODFCellProcessor) -----------------------
+    def odf_config(self, phi1_increments: int, phi2_increments: int, gamma_increments: int, shell_cutoff: float):
+        """All increments 0 switch the sampling off and free the device arrays."""
+        self._chk(self.lib.ls1hip_odf_config(self.ctx, int(phi1_increments), int(phi2_increments), int(gamma_increments),
+                                             float(shell_cutoff)))
+
+    def odf_layout(self) -> int:
+        """Words per array, W = phi1 * phi2 * gamma + 1 (0 when off)."""
+        w = C.c_size_t()
+        self._chk(self.lib.ls1hip_odf_layout(self.ctx, C.byref(w)))
+        return w.value
+
+    def odf_sample(self):
+        """One traversal over the current positions and orientations (the state rules of rdf_sample)."""
+        self._chk(self.lib.ls1hip_odf_sample(self.ctx))
+
+    def odf_read(self):
+        """LOCAL counts of this rank: hist uint64 [2, 2, W], hist[a][b] = the reference's array ODF<a+1><b+1>; samples."""
+        W = self.odf_layout()
+        hist = np.zeros(4 * W, dtype=np.uint64); smp = C.c_uint64()
+        self._chk(self.lib.ls1hip_odf_read(self.ctx, hist.ctypes.data_as(capi._u64p), 4 * W, C.byref(smp)))
+        return dict(hist=hist.reshape(2, 2, W), samples=int(smp.value))
+
+    def odf_reset(self):
+        self._chk(self.lib.ls1hip_odf_reset(self.ctx))
+
     # -- spatial profiles (ls1hip_profile_*: the reference's SpatialProfile plugin) ---------------------------------------------
     PROF_CARTESIAN, PROF_CYLINDER = 0, 1
     PROF_VELOCITY, PROF_VELOCITY3D, PROF_TEMPERATURE, PROF_VIRIAL = 1, 2, 4, 8

@@ -166,6 +166,120 @@ def _g5(x) -> str:
     return "%.5g" % x
 
 
+class ODFCellProcessor(CellProcessor):
+    """ODFCellProcessor(cutoffRadius, odf) — adapter/ODFCellProcessor.h: the pair loops (ODFCellProcessor.cpp:16-81) are one sampling
+    pass on the device (LinkedCells.traverseCells)."""
+
+    def __init__(self, cutoffRadius: float, odf: "ODF"):
+        super().__init__(cutoffRadius, cutoffRadius)
+        self._odf = odf
+
+
+_ODF_NOTE = ("//The output is to be interpreted as follows: an orientation with a value of ODF_normed = 1 has the same probability as "
+             "random orientation. ODF_normed = 1.4 means 40% higher probability than random orientation, 0.4 means 60% lower "
+             "probability than random orientation etc.\n")
+
+
+class ODF:
+    """The reference's ODF plugin (io/ODF.h, io/ODF.cpp) over the device arrays: keyword arguments = the nodes ODF::readXML reads
+    (ODF.cpp:6-24); the pairings come from the component set (ODF::init, ODF.cpp:26-79)."""
+
+    def __init__(self, components: ComponentSet, cutoffRadius: float, *, writefrequency: int = 1, initstatistics: int = 0,
+                 recordingtimesteps: int = 1, outputprefix: str = "mardyn", phi1increments: int = 1, phi2increments: int = 1,
+                 gammaincrements: int = 1, shellcutoff: float = 1.0):
+        self._writeFrequency = int(writefrequency)
+        self._initStatistics = int(initstatistics)
+        self._recordingTimesteps = int(recordingtimesteps)
+        self._outputPrefix = str(outputprefix)
+        self._phi1Increments, self._phi2Increments = int(phi1increments), int(phi2increments)
+        self._gammaIncrements = int(gammaincrements)
+        self._shellCutOff = float(shellcutoff)
+        numDipolar = sum(1 for c in components.components if len(c.dipoles) == 1)
+        self._numPairs = numDipolar * numDipolar
+        self._numElements = self._phi1Increments * self._phi2Increments * self._gammaIncrements + 1
+        self._cellProcessor = ODFCellProcessor(cutoffRadius, self)
+        self._engine = None
+        self._readStartingStep = False
+        self._ODF = np.zeros((2, 2, self._numElements), dtype=np.uint64)  # [a][b] = _ODF<a+1><b+1>
+
+    def _configure(self, engine: DeviceEngine):
+        if self._engine is not engine:
+            engine.odf_config(self._phi1Increments, self._phi2Increments, self._gammaIncrements, self._shellCutOff)
+            self._engine = engine
+
+    # --- ODF::afterForces, ODF.cpp:81-85
+    def afterForces(self, particleContainer, domainDecomp, simstep: int):
+        if simstep > self._initStatistics and simstep % self._recordingTimesteps == 0:
+            particleContainer.traverseCells(self._cellProcessor)
+
+    # --- ODF::collect, ODF.cpp:333-384: local counts of the device -> global values (summed over the ranks by a decomposition
+    # that offers odf_collect, decomp.py)
+    def collect(self, domainDecomp=None):
+        if self._engine is None:
+            return
+        collect = getattr(domainDecomp, "odf_collect", None)
+        self.setGlobal((collect(self._engine) if collect else self._engine.odf_read())["hist"])
+
+    def setGlobal(self, hist):
+        """Global arrays [2, 2, W] as DeviceEngine.odf_read / decomp.odf_collect return them under "hist"."""
+        self._ODF = np.asarray(hist, dtype=np.uint64).reshape(2, 2, self._numElements).copy()
+
+    # --- ODF::reset, ODF.cpp:104-121
+    def reset(self):
+        self._ODF[:] = 0
+        if self._engine is not None:
+            self._engine.odf_reset()
+
+    # --- ODF::endStep, ODF.cpp:87-102: nothing at the first call (a resumed run would overwrite the last file of the previous one)
+    def endStep(self, particleContainer, domainDecomp, domain, simstep: int, directory: str = "."):
+        if not self._readStartingStep:
+            self._readStartingStep = True
+            return
+        if simstep > self._initStatistics and simstep % self._writeFrequency == 0:
+            self.collect(domainDecomp)
+            if (domainDecomp.getRank() if hasattr(domainDecomp, "getRank") else 0) == 0:
+                self.output(domain, simstep, directory)
+            self.reset()
+
+    # --- ODF::output, ODF.cpp:386-506: one file for one dipolar component (the array 11 whatever the id of that component: a lone
+    # single-dipole component with id 1 counts into 22 and leaves .ODF11 without counts), four files otherwise
+    def output(self, domain, timestep: int, directory: str = "."):
+        import os
+
+        P1, P2, G, W = self._phi1Increments, self._phi2Increments, self._gammaIncrements, self._numElements
+        prefix = os.path.join(directory, "%s%07d" % (self._outputPrefix, timestep))
+        head = "//Output generated by ODF plugin\n" + _ODF_NOTE + "//Angular distribution at time step = %d for component pairing pairing " % timestep
+        if self._numPairs == 1:
+            files = [("11", (0, 0), "11\n", "cosPhi1\tcosPhi2\tGamma12\tODF_normed\n")]
+            prec = 6
+        else:
+            cos = "cosPhi1\tcosPhi2\tcosGamma12\tODF_normed\n"
+            files = [("11", (0, 0), "11.\n", cos), ("12", (0, 1), "12\n", cos), ("22", (1, 1), "22\n", "phi1\tphi2\tgamm12\tODF_normed\n"),
+                     ("21", (1, 0), "21\n", cos)]
+            prec = 5
+        fmt = lambda x: ("-nan" if np.signbit(x) else "nan") if x != x else "%.*g" % (prec, x)  # noqa: E731  operator<< at precision(prec)
+        rows = []
+        cosPhi1, cosPhi2, Gamma12 = 1. + 1. / P1, 1. - 2. / P2, 0.
+        for i in range(W - 1):
+            Gamma12 += np.pi / G
+            if i % G == 0:
+                cosPhi2 -= 2. / P2
+                Gamma12 = 0.5 * np.pi / G
+            if i % (G * P2) == 0:
+                cosPhi1 -= 2. / P1
+                cosPhi2 = 1. - 1. / P2
+            rows.append("%s\t%s\t%s\t" % (fmt(cosPhi1), fmt(cosPhi2), fmt(Gamma12)))
+        names = []
+        for tag, (a, b), end, columns in files:
+            h = self._ODF[a, b]
+            average = float(h[1:].astype(np.float64).sum()) / (float(W) - 1.)
+            with open(prefix + ".ODF" + tag, "w") as fh:
+                fh.write(head + end + columns)
+                fh.write("".join(r + fmt(_div(float(h[i + 1]), average)) + "\n" for i, r in enumerate(rows)))
+            names.append(prefix + ".ODF" + tag)
+        return names
+
+
 def _div(a, b) -> float:
     """IEEE division (the reference divides by counters that may be zero)"""
     with np.errstate(all="ignore"):
@@ -757,6 +871,11 @@ class LinkedCells:
 
     # --- LinkedCells::traverseCells, LinkedCells.cpp:564-575
     def traverseCells(self, cellProcessor: CellProcessor):
+        if isinstance(cellProcessor, ODFCellProcessor):
+            # the ODF traversal: one sampling pass over the same cells (arrays stay on the device until ODF::collect)
+            cellProcessor._odf._configure(self.engine)
+            self.engine.odf_sample()
+            return
         if isinstance(cellProcessor, RDFCellProcessor):
             # the RDF traversal: one sampling pass over the same cells (histograms stay on the device until RDF::collectRDF)
             cellProcessor.initTraversal()
