@@ -403,6 +403,42 @@ int ls1hip_odf_reset(ls1hip_ctx* ctx);
  * every step s with s > odf_from && s % odf_every == 0 (ODF.cpp:82), s counted as for "rdf_every", at the place of the RDF pass;
  * an error without a configuration.  Read-only option "odf_lds_words": the 4 W up to which a workgroup keeps the arrays in LDS. */
 
+/* ---- cavity detection ----------------------------------------------------------------------------------------------
+ * The reference's CavityWriter plugin (io/CavityWriter.{h,cpp}) and its CavityEnsemble (ensemble/CavityEnsemble.{h,cpp}): a regular
+ * lattice of Nx x Ny x Nz test nodes over the control volume [cb, ct) (default: the whole domain), node (tx, ty, tz) at
+ * cb_d + (0.5009756 + t_d) (ct_d - cb_d) / N_d with the id tid = tx Ny Nz + ty Nz + tz + 1 (CavityEnsemble.cpp:158-171).  Per node
+ * the number of container entries j with dd = dx dx + dy dy + dz dz < RR, RR = (double)((float)radius * (float)radius)
+ * (setSystem, :49-51; countNeighbours, :280-311), where an entry counts iff it lies in the GLOBAL box, 0 <= r_j,d < L_d (the search
+ * box clamped to [0, L], :289-292, and the region iterator's lo <= r < hi): NO periodic images — a node near a face sees fewer
+ * neighbours — while halo copies received from a neighbouring rank count; ALL components count (the plugin's componentid list only
+ * names output files); an entry whose id equals the node's tid is skipped (:298, an id clash of the reference, kept so that files
+ * match).  A node is active (a cavity) iff count <= maxNeighbours (decideActivity, :254-259).
+ *
+ * ls1hip_cavity_config: CavityWriter::readXML (CavityWriter.cpp:40-90) + CavityEnsemble::setSystem / setControlVolume /
+ *   setSubdomain / init (CavityEnsemble.cpp:49-112,135-160).  cv_min = cv_max = NULL: the whole domain.  This rank's nodes are
+ *   t_d = round(N_d minredco_d - 0.0009756) ... round(N_d maxredco_d - 0.0009756) - 1 with the reduced coordinates of the context's
+ *   subdomain held in float (:82-93,144-145), cut to [0, N_d).  LS1HIP_EINVAL for radius <= 0, radius > r_c (cells and halo shell
+ *   guarantee r_c only), N_d <= 0, maxNeighbours <= 0 (CavityWriter.cpp:41-65), more than 2^32 - 1 nodes, an empty control volume or
+ *   one that leaves the domain (:78-90). */
+int ls1hip_cavity_config(ls1hip_ctx* ctx, int nx, int ny, int nz, int max_neighbours, float radius, const double cv_min[3],
+						 const double cv_max[3]);
+/* One CavityEnsemble::cavityStep (CavityEnsemble.cpp:313-330, called from CavityWriter::afterForces, CavityWriter.cpp:160-174) on the
+ * CURRENT positions.  State: that of ls1hip_rdf_sample (binned, halo valid — between two list builds the refreshed one —, no split
+ * pass in flight); any cells_in_cutoff.  Options "cavity_counts" (1: exact counts, no early exit; default 0: flags only) and
+ * "cavity_chunk" (container entries per LDS staging chunk, 0 = read-only option "cavity_chunk_max").  Timer "cavity". */
+int ls1hip_cavity_sample(ls1hip_ctx* ctx);
+/* Result of the last sample: lo[3], n[3] = this rank's range of the lattice (minlu, maxlu - minlu + 1); flags[n0 n1 n2] (1: active)
+ * and counts[n0 n1 n2] in ascending tid of that range — the order of CavityEnsemble::activeParticleContainer (:271-278) that
+ * CavityWriter::endStep writes rank by rank (CavityWriter.cpp:211-235); counts: LS1HIP_EINVAL unless that sample ran in count
+ * mode; *n_active = this rank's active.size(), the input of communicateNumCavities (:221-229).  Every pointer may be NULL. */
+int ls1hip_cavity_read(ls1hip_ctx* ctx, uint32_t lo[3], uint32_t n[3], uint8_t* flags, uint32_t* counts, size_t cap, uint64_t* n_active);
+/* n_active of the samples since the configuration, oldest first (the last 4096 at most); *samples = how many. */
+int ls1hip_cavity_series(ls1hip_ctx* ctx, size_t cap, uint64_t* n_active, size_t* samples);
+/* Options "cavity_every" (_writeFrequency; default 0 = never) and "cavity_from" (Simulation::getInitStatistics): ls1hip_run samples
+ * on every step s with s >= cavity_from && s % cavity_every == 0 (CavityWriter.cpp:165), s counted as for "rdf_every", on the
+ * positions of that step's force evaluation — what afterForces sees; the pass runs directly before the force pass because a fused
+ * pass leaves the next step's positions behind.  An error without a configuration.  The trajectory does not change. */
+
 /* ---- spatial profiles ----------------------------------------------------------------------------------------------
  * The reference's SpatialProfile plugin (plugins/SpatialProfile.{h,cpp}) with the profiles of plugins/profiles/: per bin of a
  * Cartesian or cylindrical sampling grid over the GLOBAL box the number of molecules and, on request, sums of |v|, v, 3 + rotDOF,
@@ -643,7 +679,7 @@ int ls1hip_soa_forces(ls1hip_ctx* ctx, const int cell_dims[3], const uint32_t* c
 
 /* Device time (ms, HIP events on the context's compute stream) and launch count accumulated per kernel class
  * since the last reset: names[] in {"force","integrate","rebin","halo","build" (neighbour-list construction),
- * "rdf" (RDF sampling pass), "odf" (ODF sampling pass),
+ * "rdf" (RDF sampling pass), "odf" (ODF sampling pass), "cavity" (cavity pass),
  * "profile" (profile sampling pass), "insert" (insertion-energy pass)}. */
 int ls1hip_timing(ls1hip_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int ls1hip_timing_reset(ls1hip_ctx* ctx);

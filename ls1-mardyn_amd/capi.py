@@ -80,6 +80,10 @@ SYMBOLS = {
     "ls1hip_odf_sample": (C.c_int, [C.c_void_p]),
     "ls1hip_odf_read": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, _u64p]),
     "ls1hip_odf_reset": (C.c_int, [C.c_void_p]),
+    "ls1hip_cavity_config": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _dp, _dp]),
+    "ls1hip_cavity_sample": (C.c_int, [C.c_void_p]),
+    "ls1hip_cavity_read": (C.c_int, [C.c_void_p, _u32p, _u32p, C.POINTER(C.c_uint8), _u32p, C.c_size_t, _u64p]),
+    "ls1hip_cavity_series": (C.c_int, [C.c_void_p, C.c_size_t, _u64p, C.POINTER(C.c_size_t)]),
     "ls1hip_profile_config": (C.c_int, [C.c_void_p, C.c_int, _u32p, C.c_uint, C.c_int]),
     "ls1hip_profile_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]),
     "ls1hip_profile_sample": (C.c_int, [C.c_void_p]),

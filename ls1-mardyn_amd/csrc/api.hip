@@ -63,6 +63,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	dfree(c->d_steplog);
 	rdf_destroy(c);
 	odf_destroy(c);
+	cavity_destroy(c);
 	profile_destroy(c);
 	planar_destroy(c);
 	insert_destroy(c);
@@ -136,6 +137,18 @@ extern "C" int ls1hip_set_option(ls1hip_ctx* c, const char* name, long v) {
 	} else if (n == "odf_from") {
 		REQUIRE(c, v >= 0, "odf_from must be >= 0");
 		c->opt_odf_from = v;
+	} else if (n == "cavity_every") {
+		REQUIRE(c, v >= 0, "cavity_every must be >= 0 (0: ls1hip_run does not sample)");
+		c->opt_cavity_every = v;
+	} else if (n == "cavity_from") {
+		REQUIRE(c, v >= 0, "cavity_from must be >= 0");
+		c->opt_cavity_from = v;
+	} else if (n == "cavity_counts") {
+		REQUIRE(c, v == 0 || v == 1, "cavity_counts must be 0 (flags only, early exit) or 1 (exact counts)");
+		c->opt_cavity_counts = v;
+	} else if (n == "cavity_chunk") {
+		REQUIRE(c, v >= 0, "cavity_chunk must be >= 0 (0: the compiled capacity)");
+		c->opt_cavity_chunk = v;
 	} else if (n == "profile_every") {
 		REQUIRE(c, v >= 0, "profile_every must be >= 0 (0: ls1hip_run does not sample)");
 		c->opt_profile_every = v;
@@ -171,6 +184,11 @@ extern "C" int ls1hip_get_option(const ls1hip_ctx* c, const char* name, long* v)
 	else if (n == "odf_every") *v = c->opt_odf_every;
 	else if (n == "odf_from") *v = c->opt_odf_from;
 	else if (n == "odf_lds_words") *v = (long)odf_lds_words();
+	else if (n == "cavity_every") *v = c->opt_cavity_every;
+	else if (n == "cavity_from") *v = c->opt_cavity_from;
+	else if (n == "cavity_counts") *v = c->opt_cavity_counts;
+	else if (n == "cavity_chunk") *v = c->opt_cavity_chunk;
+	else if (n == "cavity_chunk_max") *v = (long)cavity_chunk_max();
 	else if (n == "profile_every") *v = c->opt_profile_every;
 	else if (n == "profile_from") *v = c->opt_profile_from;
 	else if (n == "widom_every") *v = c->opt_widom_every;
@@ -890,6 +908,7 @@ static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
 	if (n == "halo") return &c->t_halo;
 	if (n == "rdf") return &c->t_rdf;
 	if (n == "odf") return &c->t_odf;
+	if (n == "cavity") return &c->t_cavity;
 	if (n == "profile") return &c->t_profile;
 	if (n == "insert") return &c->t_insert;
 	if (n == "planar_density") return &c->t_pl_density;
@@ -914,7 +933,7 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
-	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_odf, &c->t_profile, &c->t_insert, &c->t_pl_density, &c->t_pl_tables,
+	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_odf, &c->t_cavity, &c->t_profile, &c->t_insert, &c->t_pl_density, &c->t_pl_tables,
 					 &c->t_pl_apply, &c->t_tc_measure, &c->t_tc_betas, &c->t_tc_apply}) {
 		timer_collect(*t);
 		t->total_ms = 0;

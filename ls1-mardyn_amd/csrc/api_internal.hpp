@@ -146,6 +146,8 @@ LS1_INTERNAL int rdf_sample_impl(ls1hip_ctx* c);  // api_rdf.hip: one RDF traver
 LS1_INTERNAL void rdf_destroy(ls1hip_ctx* c);
 LS1_INTERNAL int odf_sample_impl(ls1hip_ctx* c);  // api_odf.hip: one ODF traversal (ls1hip_odf_sample; ls1hip_run with "odf_every")
 LS1_INTERNAL void odf_destroy(ls1hip_ctx* c);
+LS1_INTERNAL int cavity_sample_impl(ls1hip_ctx* c);  // api_cavity.hip: one cavity pass (ls1hip_cavity_sample; ls1hip_run with "cavity_every")
+LS1_INTERNAL void cavity_destroy(ls1hip_ctx* c);
 // api_profile.hip: one profile sampling pass (ls1hip_profile_sample; ls1hip_run with "profile_every"); scaled: bin the velocities
 // multiplied by the thermostat factors on the device
 LS1_INTERNAL int profile_sample_impl(ls1hip_ctx* c, bool scaled);

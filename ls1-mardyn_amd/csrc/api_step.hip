@@ -1004,6 +1004,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	REQUIRE(c, c->forces_valid, "initial forces required (rebin, halo, forces) before ls1hip_run");
 	REQUIRE(c, !c->opt_rdf_every || c->rdf_bins > 0, "option rdf_every is set but RDF sampling is not configured (ls1hip_rdf_config)");
 	REQUIRE(c, !c->opt_odf_every || c->odf_phi > 0, "option odf_every is set but ODF sampling is not configured (ls1hip_odf_config)");
+	REQUIRE(c, !c->opt_cavity_every || c->d_cav_flags, "option cavity_every is set but cavity detection is not configured (ls1hip_cavity_config)");
 	REQUIRE(c, !c->opt_profile_every || c->prof_bins > 0, "option profile_every is set but profile sampling is not configured (ls1hip_profile_config)");
 	REQUIRE(c, !c->opt_widom_every || c->wd.n > 0, "option widom_every is set but Widom sampling is not configured (ls1hip_widom_config)");
 	HIPCHK(c, hipSetDevice(c->device));
@@ -1079,6 +1080,9 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		const bool rdf_now = c->opt_rdf_every > 0 && simstep % (unsigned long)c->opt_rdf_every == 0;
 		// ODF::afterForces (ODF.cpp:81-85): simstep > _initStatistics && simstep % _recordingTimesteps == 0; same place, the pass only reads
 		const bool odf_now = c->opt_odf_every > 0 && simstep > (unsigned long)c->opt_odf_from && simstep % (unsigned long)c->opt_odf_every == 0;
+		// CavityWriter::afterForces (CavityWriter.cpp:160-174): simstep >= getInitStatistics() && simstep % _writeFrequency == 0 counts on
+		// the positions of this step's force evaluation; same place (behind a fused pass they would be gone), the pass only reads
+		const bool cavity_now = c->opt_cavity_every > 0 && simstep >= (unsigned long)c->opt_cavity_from && simstep % (unsigned long)c->opt_cavity_every == 0;
 		// Widom test insertions: same place, same step counting; the pass only reads
 		const bool widom_now = c->opt_widom_every > 0 && simstep % (unsigned long)c->opt_widom_every == 0;
 		if (verlet) {
@@ -1087,17 +1091,19 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			if ((rc = ls1hip_update(c, nullptr))) return rc;
 			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			if (odf_now && (rc = odf_sample_impl(c))) return rc;
+			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
 			if (widom_now && (rc = widom_sample_impl(c))) return rc;
 			// unfused steps (the last one; every step of an NVT run): the pass still does the post-force kick + sum m v^2
 			rc = advanced ? ls1hip_forces_list(c, 0, dt, nullptr, nullptr)
 						  : forces_list_impl(c, 0, list_kick ? dt : 0., list_kick, nullptr, nullptr);
-		} else if (c->opt_overlap_halo == 2 || (c->opt_overlap_halo && (rdf_now || odf_now || widom_now))) {
+		} else if (c->opt_overlap_halo == 2 || (c->opt_overlap_halo && (rdf_now || odf_now || cavity_now || widom_now))) {
 			if ((rc = ls1hip_rebin(c))) return rc;
 			// halo first, then the inner and the boundary cells as two passes of the same stream (also the order of a sampling
 			// step of mode 1: the RDF pass needs the halo before the first force pass moves anything)
 			if ((rc = ls1hip_halo(c))) return rc;
 			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			if (odf_now && (rc = odf_sample_impl(c))) return rc;
+			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
 			if (widom_now && (rc = widom_sample_impl(c))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 1, dt, nullptr, nullptr) : ls1hip_forces(c, 1, nullptr, nullptr);
 			if (rc) return rc;
@@ -1114,6 +1120,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 			if ((rc = ls1hip_halo(c))) return rc;
 			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
 			if (odf_now && (rc = odf_sample_impl(c))) return rc;
+			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
 			if (widom_now && (rc = widom_sample_impl(c))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 0, dt, nullptr, nullptr) : ls1hip_forces(c, 0, nullptr, nullptr);
 		}

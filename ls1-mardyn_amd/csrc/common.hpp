@@ -245,6 +245,27 @@ struct OdfParams {
 	unsigned long long* g_hist;  // [4][W], arrays in the order 11 12 21 22
 };
 
+// cavity detection (kernels_cavity.hip): io/CavityWriter.cpp, ensemble/CavityEnsemble.cpp:114-219,254-330
+struct CavityParams {
+	Grid g;
+	const double *x, *y, *z;  // current positions, owned + halo segment
+	const uint64_t* id;
+	const uint32_t *cell_begin, *cell_end;
+	double glen[3];            // global box: an entry counts iff 0 <= r_d < glen[d] (countNeighbours' clamped search box + inBox)
+	double cb[3], h[3];        // control_bottom, grid_spacing (CavityEnsemble.cpp:158)
+	uint32_t N[3];             // Nx Ny Nz of the whole lattice (tid = tx Ny Nz + ty Nz + tz + 1, :169)
+	uint32_t lo[3], n[3];      // this rank's sub-lattice: minlu, maxlu - minlu + 1 (:144-145)
+	uint32_t tile[3], nt[3];   // nodes per tile and tiles per dimension; tile[0] tile[1] tile[2] <= 256
+	uint32_t ntiles;
+	double RR;                 // (double)((float)radius * (float)radius), setSystem (:51)
+	double rfilter, rwalk;     // inflation of the tile box: the candidate pre-filter (just above sqrt(RR)), the cell walk (+ list drift)
+	uint32_t max_nb;           // maxNeighbours
+	uint32_t chunk;            // container entries scanned per staging chunk, 1 ... cavity_chunk_max()
+	uint8_t* flags;            // [n0 n1 n2] 1: active (count <= maxNeighbours), tid order of the sub-lattice
+	uint32_t* counts;          // count mode: [n0 n1 n2] neighbour counts; else nullptr
+	unsigned long long* n_active;  // one word, zeroed by the launcher's clear kernel
+};
+
 // spatial profiles (kernels_profile.hip): plugins/SpatialProfile.{h,cpp}, plugins/profiles/*
 struct ProfParams {
 	int mode;           // LS1HIP_PROF_CARTESIAN / LS1HIP_PROF_CYLINDER
@@ -506,6 +527,18 @@ struct ls1hip_ctx {
 	uint64_t odf_samples = 0;
 	long opt_odf_every = 0, opt_odf_from = 0;
 	ls1::Timer t_odf;
+	// cavity detection (ls1hip_cavity_*; kernels_cavity.hip): cav holds lattice, sub-lattice, tile shape and radius of the configuration
+	// (ntiles = 0: off); flags, counts and the n_active series live in d_cav_flags / d_cav_counts / d_cav_series
+	ls1::CavityParams cav{};
+	double cav_radius = 0.;
+	double cav_dom[6] = {0, 0, 0, 0, 0, 0};  // subdomain (min, max) the sub-lattice was computed from
+	uint8_t* d_cav_flags = nullptr;
+	uint32_t* d_cav_counts = nullptr;
+	unsigned long long* d_cav_series = nullptr;  // n_active of sample k at [k % CAV_SERIES] (ring)
+	uint64_t cav_samples = 0;
+	bool cav_last_counts = false;  // the last sample ran in count mode
+	long opt_cavity_every = 0, opt_cavity_from = 0, opt_cavity_counts = 0, opt_cavity_chunk = 0;
+	ls1::Timer t_cavity;
 	// spatial profiles (ls1hip_profile_*; kernels_profile.hip): one device table, layout of ProfParams
 	int prof_mode = 0, prof_comp = -1;
 	unsigned prof_quant = 0;
@@ -687,6 +720,11 @@ bool launch_rdf(const ForceParams& p, RdfParams r, bool has_rot, double mean_per
 // ODF sampling pass over all bricks (kernels_odf.hip); fills o.hist_lds; false: the grid cannot be served (hw != 1)
 bool launch_odf(const ForceParams& p, OdfParams o, bool has_rot, double mean_per_cell, hipStream_t s);
 size_t odf_lds_words();  // most u32 words (4 W) a workgroup keeps in LDS (above it: global atomics)
+// cavity pass over the tiles of the node lattice (kernels_cavity.hip); the launcher clears *p.n_active first
+void launch_cavity(const CavityParams& p, hipStream_t s);
+size_t cavity_chunk_max();  // compile-time capacity of the LDS staging chunk (container entries)
+// tile shape (nodes per dimension, product <= 256) for a sub-lattice of n nodes with spacings h and search radius R
+void cavity_tile_shape(const uint32_t n[3], const double h[3], double R, uint32_t tile[3]);
 // spatial-profile sampling pass over the owned molecules (kernels_profile.hip); n_cap: launch bound (n_real is read on the device)
 void launch_profile(const ProfParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
 size_t profile_lds_words();  // largest table a workgroup keeps in LDS (above it: run-merged global atomics)

@@ -491,6 +491,50 @@ def odf_collect(engine, dist=None, group=None, device=None):
     return dict(local, hist=t.cpu().numpy().astype(np.uint64).reshape(local["hist"].shape))
 
 
+def cavity_collect(engine, N, dist=None, group=None, device=None):
+    """CavityEnsemble::communicateNumCavities (ensemble/CavityEnsemble.cpp:221-229: ONE all-reduce of active.size()) and what
+    CavityWriter::endStep's rank-by-rank append amounts to (io/CavityWriter.cpp:211-235): every rank's flags with their lattice range,
+    gathered.  Returns dict(lo = 0, n = N, flags = the global lattice uint8 [Nx, Ny, Nz], n_active = the global count, pieces =
+    [(lo, n, flags)] in rank order = the file order of the reference).  Without an initialised process group: the local result with
+    its one piece (cavity_assemble joins the pieces of several contexts of one process)."""
+    local = engine.cavity_read()
+    N = tuple(int(k) for k in N)
+    pieces, n_active = [(local["lo"], local["n"], local["flags"])], local["n_active"]
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return dict(local, pieces=pieces)
+    import torch
+
+    to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
+    world = dist.get_world_size(group)
+    total = to(torch.tensor([n_active], dtype=torch.int64))
+    dist.all_reduce(total, group=group)
+    n_active = int(total.cpu()[0])
+    meta = [to(torch.zeros(6, dtype=torch.int64)) for _ in range(world)]
+    dist.all_gather(meta, to(torch.from_numpy(np.concatenate([local["lo"], local["n"]]).astype(np.int64))), group=group)
+    meta = [m.cpu().numpy() for m in meta]
+    width = max(int(m[3:].prod()) for m in meta)
+    mine = np.zeros(width, dtype=np.uint8)
+    mine[:local["flags"].size] = local["flags"].reshape(-1)
+    parts = [to(torch.zeros(width, dtype=torch.uint8)) for _ in range(world)]
+    dist.all_gather(parts, to(torch.from_numpy(mine)), group=group)
+    pieces = [(m[:3], m[3:], p.cpu().numpy()[:int(m[3:].prod())].reshape(tuple(int(k) for k in m[3:]))) for m, p in zip(meta, parts)]
+    return cavity_assemble(pieces, N, n_active)
+
+
+def cavity_assemble(pieces, N, n_active):
+    """The global lattice from the (lo, n, flags) pieces of the ranks; the pieces must partition it."""
+    flags, seen = np.zeros(N, dtype=np.uint8), np.zeros(N, dtype=np.uint8)
+    for lo, n, f in pieces:
+        sl = tuple(slice(int(lo[d]), int(lo[d] + n[d])) for d in range(3))
+        flags[sl] = f
+        seen[sl] += 1
+    if not (seen == 1).all():
+        raise ValueError("the node ranges of the ranks do not partition the %d x %d x %d lattice" % N)
+    return dict(lo=np.zeros(3, dtype=np.int64), n=np.array(N, dtype=np.int64), flags=flags, n_active=int(n_active), pieces=pieces)
+
+
 def profile_collect(engine, dist=None, group=None, device=None):
     """The collective of SpatialProfile::endStep (plugins/SpatialProfile.cpp:286-310): the local tables of every rank summed by
     at most two all-reduces — one int64 block {n, dof}, one float64 block {ekin, vabs, v3, vi3} (the reference appends one value per

@@ -388,6 +388,43 @@ class DeviceEngine:
     def odf_reset(self):
         self._chk(self.lib.ls1hip_odf_reset(self.ctx))
 
+    # -- cavity detection (ls1hip_cavity_*: the reference's CavityWriter plugin + CavityEnsemble) -------------------------------
+    def cavity_config(self, nx: int, ny: int, nz: int, max_neighbours: int, radius: float, cv_min=None, cv_max=None):
+        """Lattice of nx x ny x nz nodes over the control volume (default: the whole domain); radius is the reference's float."""
+        lo = capi.f64(cv_min, (3,)) if cv_min is not None else None
+        hi = capi.f64(cv_max, (3,)) if cv_max is not None else None
+        self._chk(self.lib.ls1hip_cavity_config(self.ctx, int(nx), int(ny), int(nz), int(max_neighbours), float(radius),
+                                                capi.dptr(lo), capi.dptr(hi)))
+
+    def cavity_sample(self):
+        """One neighbour count of every node of this rank on the current positions (the state rules of rdf_sample)."""
+        self._chk(self.lib.ls1hip_cavity_sample(self.ctx))
+
+    def cavity_read(self, counts: bool = False):
+        """Last sample of this rank: lo, n (its range of the lattice), flags uint8 [n0, n1, n2] (1: cavity), n_active, and with
+        counts=True (only after a sample in count mode) counts uint32 [n0, n1, n2]."""
+        lo = np.zeros(3, dtype=np.uint32); n = np.zeros(3, dtype=np.uint32); act = C.c_uint64()
+        self._chk(self.lib.ls1hip_cavity_read(self.ctx, lo.ctypes.data_as(capi._u32p), n.ctypes.data_as(capi._u32p), None, None, 0, None))
+        nn = int(n.astype(np.int64).prod())
+        flags = np.zeros(nn, dtype=np.uint8)
+        cnt = np.zeros(nn, dtype=np.uint32) if counts else None
+        self._chk(self.lib.ls1hip_cavity_read(self.ctx, None, None, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              cnt.ctypes.data_as(capi._u32p) if counts else None, nn, C.byref(act)))
+        shape = tuple(int(k) for k in n)
+        out = dict(lo=lo.astype(np.int64), n=n.astype(np.int64), flags=flags.reshape(shape), n_active=int(act.value))
+        if counts:
+            out["counts"] = cnt.reshape(shape)
+        return out
+
+    def cavity_series(self):
+        """n_active of every sample since cavity_config (the last 4096 at most), oldest first: uint64 array."""
+        k = C.c_size_t()
+        self._chk(self.lib.ls1hip_cavity_series(self.ctx, 0, None, C.byref(k)))
+        out = np.zeros(k.value, dtype=np.uint64)
+        if k.value:
+            self._chk(self.lib.ls1hip_cavity_series(self.ctx, k.value, out.ctypes.data_as(capi._u64p), C.byref(k)))
+        return out
+
     # -- spatial profiles (ls1hip_profile_*: the reference's SpatialProfile plugin) ---------------------------------------------
     PROF_CARTESIAN, PROF_CYLINDER = 0, 1
     PROF_VELOCITY, PROF_VELOCITY3D, PROF_TEMPERATURE, PROF_VIRIAL = 1, 2, 4, 8

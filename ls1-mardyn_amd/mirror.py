@@ -476,6 +476,85 @@ def _g6(x) -> str:
     return "%.6g" % x
 
 
+class CavityWriter:
+    """The reference's CavityWriter plugin (io/CavityWriter.{h,cpp}) over the device pass: keyword arguments = the nodes
+    CavityWriter::readXML reads (CavityWriter.cpp:18-111); ControlVolume = (x0, x1, y0, y1, z0, z1) or None (the whole domain);
+    componentid: the ids that name the output files (every molecule counts whatever its component).  numTimesteps: the run length
+    the incremental file numbers are sized by (Simulation::getNumTimesteps); initStatistics: Simulation::getInitStatistics."""
+
+    _ELEMENT = ("C ", "N ", "O ", "F ")  # by component id, "Ne " above (CavityWriter.cpp:223-227)
+
+    def __init__(self, length, *, writefrequency: int = 1, outputprefix: str = "mardyn", incremental: int = 1, maxNeighbours: int,
+                 radius: float, Nx: int, Ny: int, Nz: int, ControlVolume=None, componentid=(0,), numTimesteps: int = 1,
+                 initStatistics: int = 0):
+        self._length = np.asarray(length, dtype=np.float64).reshape(3)
+        self._writeFrequency, self._outputPrefix, self._incremental = int(writefrequency), str(outputprefix), int(incremental) != 0
+        self._maxNeighbors, self._radius = int(maxNeighbours), float(np.float32(radius))
+        self._N = (int(Nx), int(Ny), int(Nz))
+        cv = (0., self._length[0], 0., self._length[1], 0., self._length[2]) if ControlVolume is None else ControlVolume
+        self._controlVolume = tuple(float(v) for v in cv)
+        self._componentids = sorted(set(int(k) for k in componentid))  # a std::map: ascending ids
+        self._numTimesteps, self._initStatistics = int(numTimesteps), int(initStatistics)
+        self._engine = None
+        self._pieces = []  # (lo, n, flags [n0, n1, n2]) of every rank, in rank order: the active sets
+        self._numCavities = 0
+
+    # --- CavityWriter::init, CavityWriter.cpp:113-146
+    def init(self, engine: DeviceEngine):
+        cv = self._controlVolume
+        engine.cavity_config(*self._N, self._maxNeighbors, self._radius, cv[0::2], cv[1::2])
+        self._engine = engine
+
+    # --- CavityWriter::afterForces, CavityWriter.cpp:160-174: cavityStep + communicateNumCavities
+    def afterForces(self, particleContainer, domainDecomp, simstep: int):
+        if simstep >= self._initStatistics and simstep % self._writeFrequency == 0:
+            self._engine.cavity_sample()
+            collect = getattr(domainDecomp, "cavity_collect", None)
+            self.setGlobal(collect(self._engine, self._N) if collect else self._engine.cavity_read())
+
+    def setGlobal(self, res):
+        """The active sets from DeviceEngine.cavity_read (one rank) or decomp.cavity_collect (pieces of all ranks, global n_active)."""
+        self._pieces = list(res.get("pieces") or [(res["lo"], res["n"], res["flags"])])
+        self._numCavities = int(res["n_active"])
+
+    def nodePositions(self):
+        """tq of every node (CavityEnsemble.cpp:158-171): float64 [Nx, Ny, Nz, 3]."""
+        cv = self._controlVolume
+        ax = [cv[2 * d] + (0.5009756 + np.arange(self._N[d])) * ((cv[2 * d + 1] - cv[2 * d]) / float(self._N[d])) for d in range(3)]
+        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1)
+
+    def fileName(self, cid: int, simstep: int) -> str:
+        name = "%s-c%d" % (self._outputPrefix, cid)
+        if self._incremental:
+            # (int) ceil(log(double(numTimesteps / _writeFrequency)) / log(10.)), aligned_number (CavityWriter.cpp:188-193)
+            num_digits = int(np.ceil(_div(np.log(float(self._numTimesteps // self._writeFrequency)), np.log(10.))))
+            name += "-" + "%0*d" % (max(num_digits, 0), simstep // self._writeFrequency)
+        return name + ".cav.xyz"
+
+    def render(self, cid: int) -> str:
+        """The text of one file: the global number of cavities, "comment line", then rank by rank (CavityWriter.cpp:211-235) one line
+        per active node in ascending tid (z fastest)."""
+        el = self._ELEMENT[cid] if 0 <= cid < 4 else "Ne "
+        pos, out = self.nodePositions(), ["%d\ncomment line\n" % self._numCavities]
+        for lo, n, flags in self._pieces:
+            r = pos[lo[0]:lo[0] + n[0], lo[1]:lo[1] + n[1], lo[2]:lo[2] + n[2]][np.asarray(flags).reshape(tuple(n)) != 0]
+            out += ["%s%s\t%s\t%s\n" % (el, _g6(p[0]), _g6(p[1]), _g6(p[2])) for p in r]
+        return "".join(out)
+
+    # --- CavityWriter::endStep, CavityWriter.cpp:176-237: writes whenever simstep % _writeFrequency == 0, also before initStatistics
+    # (the active set is then whatever it was)
+    def endStep(self, particleContainer, domainDecomp, domain, simstep: int, directory: str = "."):
+        if simstep % self._writeFrequency != 0:
+            return []
+        names = []
+        if (domainDecomp.getRank() if hasattr(domainDecomp, "getRank") else 0) == 0:
+            for cid in self._componentids:
+                names.append(os.path.join(directory, self.fileName(cid, simstep)))
+                with open(names[-1], "w") as fh:
+                    fh.write(self.render(cid))
+        return names
+
+
 class Planar:
     """The reference's planar long-range correction (longRange/Planar.{h,cpp}) over the device tables: readXML-style arguments
     (slabs, frequency, region = (left, right) with right = "box" allowed, writecontrol start / frequency / stop), calculateLongRange
