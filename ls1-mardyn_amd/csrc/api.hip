@@ -71,7 +71,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	if (c->d_ingest) hipFree(c->d_ingest);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_flag) hipHostFree((void*)c->h_flag);
-	timer_free(c->t_force); timer_free(c->t_integrate); timer_free(c->t_rebin); timer_free(c->t_halo); timer_free(c->t_build);
+	for (const TimerName& t : TIMERS) timer_free(c->*t.t);
 	hipStreamDestroy(c->stream);
 	if (c->stream2) hipStreamDestroy(c->stream2);
 	if (c->ev_owned) hipEventDestroy(c->ev_owned);
@@ -102,62 +102,59 @@ bool can_list_kick_ms(const ls1hip_ctx* c) {
 		   !c->opt_count_pairs && !c->has_remote;
 }
 
+// the options that are plain numbers in a range: one row serves ls1hip_set_option and ls1hip_get_option; `must` completes
+// "<name> must be ..."
+struct RangeOption {
+	const char* name;
+	long ls1hip_ctx::*v;
+	long min, max;
+	const char* must;
+};
+constexpr long NO_MAX = 0x7fffffffffffffffL;
+constexpr RangeOption RANGE_OPTIONS[] = {
+	{"force_kernel", &ls1hip_ctx::opt_force_kernel, 0, 4, "0..4 (LS1HIP_FK_*)"},
+	{"overlap_halo", &ls1hip_ctx::opt_overlap_halo, 0, 2, "0, 1 or 2"},
+	{"precision", &ls1hip_ctx::opt_precision, 0, 2, "0 (FP64), 1 (SPDP) or 2 (SPSP)"},
+	{"rdf_every", &ls1hip_ctx::opt_rdf_every, 0, NO_MAX, ">= 0 (0: ls1hip_run does not sample)"},
+	{"odf_every", &ls1hip_ctx::opt_odf_every, 0, NO_MAX, ">= 0 (0: ls1hip_run does not sample)"},
+	{"odf_from", &ls1hip_ctx::opt_odf_from, 0, NO_MAX, ">= 0"},
+	{"cavity_every", &ls1hip_ctx::opt_cavity_every, 0, NO_MAX, ">= 0 (0: ls1hip_run does not sample)"},
+	{"cavity_from", &ls1hip_ctx::opt_cavity_from, 0, NO_MAX, ">= 0"},
+	{"cavity_counts", &ls1hip_ctx::opt_cavity_counts, 0, 1, "0 (flags only, early exit) or 1 (exact counts)"},
+	{"cavity_chunk", &ls1hip_ctx::opt_cavity_chunk, 0, NO_MAX, ">= 0 (0: the compiled capacity)"},
+	{"profile_every", &ls1hip_ctx::opt_profile_every, 0, NO_MAX, ">= 0 (0: ls1hip_run does not sample)"},
+	{"profile_from", &ls1hip_ctx::opt_profile_from, 0, NO_MAX, ">= 0"},
+	{"widom_every", &ls1hip_ctx::opt_widom_every, 0, NO_MAX, ">= 0 (0: ls1hip_run does not sample)"},
+};
+// ... and the switches: any value but 0 sets them
+struct SwitchOption {
+	const char* name;
+	long ls1hip_ctx::*v;
+};
+constexpr SwitchOption SWITCH_OPTIONS[] = {
+	{"compute_vi", &ls1hip_ctx::opt_vi},           {"deterministic", &ls1hip_ctx::opt_det},
+	{"count_pairs", &ls1hip_ctx::opt_count_pairs}, {"fuse_integration", &ls1hip_ctx::opt_fuse},
+	{"local_rebuild", &ls1hip_ctx::opt_local_rebuild},
+};
+
 extern "C" int ls1hip_set_option(ls1hip_ctx* c, const char* name, long v) {
 	if (!c || !name) return LS1HIP_EINVAL;
 	std::string n(name);
-	if (n == "force_kernel") {
-		REQUIRE(c, v >= 0 && v <= 4, "force_kernel must be 0..4 (LS1HIP_FK_*)");
-		c->opt_force_kernel = v;
-	} else if (n == "cells_in_cutoff") {
+	for (const RangeOption& o : RANGE_OPTIONS)
+		if (n == o.name) {
+			REQUIRE(c, v >= o.min && v <= o.max, "%s must be %s", o.name, o.must);
+			c->*o.v = v;
+			return LS1HIP_OK;
+		}
+	for (const SwitchOption& o : SWITCH_OPTIONS)
+		if (n == o.name) {
+			c->*o.v = v ? 1 : 0;
+			return LS1HIP_OK;
+		}
+	if (n == "cells_in_cutoff") {
 		REQUIRE(c, v == 1 || v == 2, "cells_in_cutoff must be 1 or 2");
 		REQUIRE(c, !c->have_domain, "cells_in_cutoff must be set before ls1hip_set_domain");
 		c->opt_cic = v;
-	} else if (n == "compute_vi") {
-		c->opt_vi = v ? 1 : 0;
-	} else if (n == "deterministic") {
-		c->opt_det = v ? 1 : 0;
-	} else if (n == "count_pairs") {
-		c->opt_count_pairs = v ? 1 : 0;
-	} else if (n == "fuse_integration") {
-		c->opt_fuse = v ? 1 : 0;
-	} else if (n == "overlap_halo") {
-		REQUIRE(c, v >= 0 && v <= 2, "overlap_halo must be 0, 1 or 2");
-		c->opt_overlap_halo = v;
-	} else if (n == "precision") {
-		REQUIRE(c, v >= 0 && v <= 2, "precision must be 0 (FP64), 1 (SPDP) or 2 (SPSP)");
-		c->opt_precision = v;
-	} else if (n == "local_rebuild") {
-		c->opt_local_rebuild = v ? 1 : 0;
-	} else if (n == "rdf_every") {
-		REQUIRE(c, v >= 0, "rdf_every must be >= 0 (0: ls1hip_run does not sample)");
-		c->opt_rdf_every = v;
-	} else if (n == "odf_every") {
-		REQUIRE(c, v >= 0, "odf_every must be >= 0 (0: ls1hip_run does not sample)");
-		c->opt_odf_every = v;
-	} else if (n == "odf_from") {
-		REQUIRE(c, v >= 0, "odf_from must be >= 0");
-		c->opt_odf_from = v;
-	} else if (n == "cavity_every") {
-		REQUIRE(c, v >= 0, "cavity_every must be >= 0 (0: ls1hip_run does not sample)");
-		c->opt_cavity_every = v;
-	} else if (n == "cavity_from") {
-		REQUIRE(c, v >= 0, "cavity_from must be >= 0");
-		c->opt_cavity_from = v;
-	} else if (n == "cavity_counts") {
-		REQUIRE(c, v == 0 || v == 1, "cavity_counts must be 0 (flags only, early exit) or 1 (exact counts)");
-		c->opt_cavity_counts = v;
-	} else if (n == "cavity_chunk") {
-		REQUIRE(c, v >= 0, "cavity_chunk must be >= 0 (0: the compiled capacity)");
-		c->opt_cavity_chunk = v;
-	} else if (n == "profile_every") {
-		REQUIRE(c, v >= 0, "profile_every must be >= 0 (0: ls1hip_run does not sample)");
-		c->opt_profile_every = v;
-	} else if (n == "widom_every") {
-		REQUIRE(c, v >= 0, "widom_every must be >= 0 (0: ls1hip_run does not sample)");
-		c->opt_widom_every = v;
-	} else if (n == "profile_from") {
-		REQUIRE(c, v >= 0, "profile_from must be >= 0");
-		c->opt_profile_from = v;
 	} else if (n == "lj_split") {
 		REQUIRE(c, v == 0 || v == 1 || v == 2 || v == 4 || v == 5 || v == 6, "lj_split must be 0 (auto), 1, 2 (list kernel lanes per molecule), 4, 5 or 6 (MFMA pre-filter variants)");
 		c->opt_lj_split = v;
@@ -170,28 +167,20 @@ extern "C" int ls1hip_set_option(ls1hip_ctx* c, const char* name, long v) {
 extern "C" int ls1hip_get_option(const ls1hip_ctx* c, const char* name, long* v) {
 	if (!c || !name || !v) return LS1HIP_EINVAL;
 	std::string n(name);
-	if (n == "force_kernel") *v = c->opt_force_kernel;
-	else if (n == "cells_in_cutoff") *v = c->opt_cic;
-	else if (n == "compute_vi") *v = c->opt_vi;
-	else if (n == "deterministic") *v = c->opt_det;
-	else if (n == "count_pairs") *v = c->opt_count_pairs;
+	for (const RangeOption& o : RANGE_OPTIONS)
+		if (n == o.name) {
+			*v = c->*o.v;
+			return LS1HIP_OK;
+		}
+	for (const SwitchOption& o : SWITCH_OPTIONS)
+		if (n == o.name) {
+			*v = c->*o.v;
+			return LS1HIP_OK;
+		}
+	if (n == "cells_in_cutoff") *v = c->opt_cic;
 	else if (n == "lj_split") *v = c->opt_lj_split;
-	else if (n == "fuse_integration") *v = c->opt_fuse;
-	else if (n == "overlap_halo") *v = c->opt_overlap_halo;
-	else if (n == "precision") *v = c->opt_precision;
-	else if (n == "local_rebuild") *v = c->opt_local_rebuild;
-	else if (n == "rdf_every") *v = c->opt_rdf_every;
-	else if (n == "odf_every") *v = c->opt_odf_every;
-	else if (n == "odf_from") *v = c->opt_odf_from;
 	else if (n == "odf_lds_words") *v = (long)odf_lds_words();
-	else if (n == "cavity_every") *v = c->opt_cavity_every;
-	else if (n == "cavity_from") *v = c->opt_cavity_from;
-	else if (n == "cavity_counts") *v = c->opt_cavity_counts;
-	else if (n == "cavity_chunk") *v = c->opt_cavity_chunk;
 	else if (n == "cavity_chunk_max") *v = (long)cavity_chunk_max();
-	else if (n == "profile_every") *v = c->opt_profile_every;
-	else if (n == "profile_from") *v = c->opt_profile_from;
-	else if (n == "widom_every") *v = c->opt_widom_every;
 	else if (n == "verlet_irregular_bricks") {
 		// bricks of the last list build that do NOT run the production path of the list force pass (region beyond the LDS staging
 		// area, list overflow, more owned molecules than the tiles cover): read back from the device on request, any precision
@@ -900,23 +889,8 @@ extern "C" int ls1hip_download_forces(ls1hip_ctx* c, size_t cap, double* F, doub
 
 // ---- measurement ---------------------------------------------------------------------------------------------------
 static Timer* timer_by_name(ls1hip_ctx* c, const char* name) {
-	std::string n(name ? name : "");
-	if (n == "force") return &c->t_force;
-	if (n == "integrate") return &c->t_integrate;
-	if (n == "rebin") return &c->t_rebin;
-	if (n == "build") return &c->t_build;
-	if (n == "halo") return &c->t_halo;
-	if (n == "rdf") return &c->t_rdf;
-	if (n == "odf") return &c->t_odf;
-	if (n == "cavity") return &c->t_cavity;
-	if (n == "profile") return &c->t_profile;
-	if (n == "insert") return &c->t_insert;
-	if (n == "planar_density") return &c->t_pl_density;
-	if (n == "planar_tables") return &c->t_pl_tables;
-	if (n == "planar_apply") return &c->t_pl_apply;
-	if (n == "tempcontrol_measure") return &c->t_tc_measure;
-	if (n == "tempcontrol_betas") return &c->t_tc_betas;
-	if (n == "tempcontrol_apply") return &c->t_tc_apply;
+	for (const TimerName& t : TIMERS)
+		if (name && !strcmp(name, t.name)) return &(c->*t.t);
 	return nullptr;
 }
 
@@ -933,8 +907,8 @@ extern "C" int ls1hip_timing(ls1hip_ctx* c, const char* name, double* total_ms, 
 
 extern "C" int ls1hip_timing_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
-	for (Timer* t : {&c->t_force, &c->t_integrate, &c->t_rebin, &c->t_halo, &c->t_build, &c->t_rdf, &c->t_odf, &c->t_cavity, &c->t_profile, &c->t_insert, &c->t_pl_density, &c->t_pl_tables,
-					 &c->t_pl_apply, &c->t_tc_measure, &c->t_tc_betas, &c->t_tc_apply}) {
+	for (const TimerName& tn : TIMERS) {
+		Timer* t = &(c->*tn.t);
 		timer_collect(*t);
 		t->total_ms = 0;
 		t->launches = 0;

@@ -14,10 +14,7 @@ static void cavity_free(ls1hip_ctx* c) {
 	c->cav_last_counts = false;
 }
 
-void cavity_destroy(ls1hip_ctx* c) {
-	cavity_free(c);
-	timer_free(c->t_cavity);
-}
+void cavity_destroy(ls1hip_ctx* c) { cavity_free(c); }
 
 // CavityWriter::readXML (CavityWriter.cpp:40-90) + CavityEnsemble::setSystem / setControlVolume / setSubdomain / init
 // (CavityEnsemble.cpp:49-112, :135-160)
@@ -89,14 +86,12 @@ extern "C" int ls1hip_cavity_config(ls1hip_ctx* c, int nx, int ny, int nz, int m
 static bool cavity_configured(const ls1hip_ctx* c) { return c->d_cav_flags != nullptr; }
 static size_t cavity_local_nodes(const ls1hip_ctx* c) { return (size_t)c->cav.n[0] * c->cav.n[1] * c->cav.n[2]; }
 
-// one CavityEnsemble::cavityStep (CavityEnsemble.cpp:313-330) over the current positions; the state rules of rdf_sample_impl, any
-// cells_in_cutoff (the cells are found from coordinates, not from a fixed neighbourhood)
+// one CavityEnsemble::cavityStep (CavityEnsemble.cpp:313-330) over the current positions; any cells_in_cutoff (the cells are found
+// from coordinates, not from a fixed neighbourhood)
 int cavity_sample_impl(ls1hip_ctx* c) {
 	REQUIRE(c, cavity_configured(c), "cavity detection is not configured (ls1hip_cavity_config)");
 	REQUIRE(c, c->cap_real, "no molecules uploaded");
-	REQUIRE(c, c->binned || (c->vl_ready && !c->has_remote), "molecules are not binned (call ls1hip_rebin)");
-	REQUIRE(c, c->halo_valid, "halo not populated (call ls1hip_halo / import_done(1), or ls1hip_halo_refresh between list builds)");
-	REQUIRE(c, !c->fused_split && !c->inner_in_flight, "a split force pass is in flight");
+	if (int rc = sample_gate(c)) return rc;
 	CavityParams P = c->cav;
 	for (int d = 0; d < 3; ++d)
 		REQUIRE(c, P.glen[d] == c->global_len[d] && c->cav_dom[d] == c->dom_min[d] && c->cav_dom[3 + d] == c->dom_max[d],
@@ -108,10 +103,10 @@ int cavity_sample_impl(ls1hip_ctx* c) {
 		int rc = dalloc(c, &c->d_cav_counts, local);
 		if (rc) return rc;
 	}
-	const MolSoA& m = c->mol[c->cur];
+	const Pos3 r = cur_pos(c);
 	P.g = c->g;
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
-	P.id = m.id;
+	P.x = r.x; P.y = r.y; P.z = r.z;
+	P.id = c->mol[c->cur].id;
 	P.cell_begin = c->d_cell_begin; P.cell_end = c->d_cell_end;
 	// the pre-filter keeps everything a node of the tile can reach (|d| <= sqrt(dd) < R, rounding far inside the 2^-40); between two
 	// list builds an entry sits in the cell of its position at build time, at most `skin` away (the local rebuild criterion bounds the
@@ -171,9 +166,5 @@ extern "C" int ls1hip_cavity_series(ls1hip_ctx* c, size_t cap, uint64_t* n_activ
 	REQUIRE(c, cap >= have, "buffer too small: %zu < %zu samples", cap, have);
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	// oldest first: a ring over the sample number
-	const size_t first = (size_t)((c->cav_samples - have) % CAV_SERIES), n1 = std::min(have, CAV_SERIES - first);
-	HIPCHK(c, hipMemcpy(n_active, c->d_cav_series + first, n1 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	if (have > n1) HIPCHK(c, hipMemcpy(n_active + n1, c->d_cav_series, (have - n1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	return LS1HIP_OK;
+	return ring_read(c, c->d_cav_series, sizeof(uint64_t), c->cav_samples, CAV_SERIES, n_active);  // a ring over the sample number
 }

@@ -160,9 +160,8 @@ extern "C" int ls1hip_import(ls1hip_ctx* c, int kind, const void* dev_buf, size_
 		REQUIRE(c, c->vl_ready, "no neighbour lists (ls1hip_verlet_build)");
 		REQUIRE(c, c->halo_import_at + n <= c->vl_imp_total, "more refresh records than halo records were imported at build time");
 		HaloArgs a = halo_args(c);
-		const MolSoA& m = c->mol[c->cur];
-		launch_refresh_import(a, (const double*)dev_buf, (uint32_t)n, c->pos_x ? c->pos_x : m.x, c->pos_x ? c->pos_y : m.y,
-							  c->pos_x ? c->pos_z : m.z, halo_stream(c));
+		const Pos3 r = cur_pos(c);
+		launch_refresh_import(a, (const double*)dev_buf, (uint32_t)n, r.x, r.y, r.z, halo_stream(c));
 		c->halo_import_at += (uint32_t)n;
 		return LS1HIP_OK;
 	}

@@ -13,29 +13,19 @@ void insert_destroy(ls1hip_ctx* c) {
 	widom_free(c);
 	dfree(c->d_ins);
 	c->ins_cap = 0;
-	timer_free(c->t_insert);
 }
 
-// the state rules of rdf_sample_impl (api_rdf.hip), and the arguments every insertion launch shares
+// the state rules of the sampling passes, and the arguments every insertion launch shares
 static int insert_params(ls1hip_ctx* c, InsertParams* out) {
 	REQUIRE(c, c->have_comp && c->have_domain && c->cap_real, "no molecules uploaded");
 	// between two builds of the neighbour lists the binning of the last build stays: a partner inside r_c of the test point now was
 	// inside r_c + skin / 2 of it at build time, and the cells are at least r_c + skin long
-	REQUIRE(c, c->binned || (c->vl_ready && !c->has_remote), "molecules are not binned (call ls1hip_rebin)");
-	REQUIRE(c, c->halo_valid, "halo not populated (call ls1hip_halo / import_done(1), or ls1hip_halo_refresh between list builds)");
-	REQUIRE(c, !c->fused_split && !c->inner_in_flight, "a split force pass is in flight");
-	const MolSoA& m = c->mol[c->cur];
+	if (int rc = sample_gate(c)) return rc;
 	InsertParams P;
 	memset(&P, 0, sizeof(P));
-	P.g = c->g;
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
-	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
-	P.cid = m.cid;
-	P.id = m.id;
-	P.cell_begin = c->d_cell_begin; P.cell_end = c->d_cell_end;
+	fill_cell_args(c, P);
+	P.id = c->mol[c->cur].id;
 	P.hsrc = c->d_halo_src;
-	P.ct = c->d_ct;
-	P.cnt = c->d_cnt;
 	P.eps24 = c->h_ct.eps24[0]; P.sig2 = c->h_ct.sig2[0]; P.shift6 = c->h_ct.shift6[0];
 	*out = P;
 	return LS1HIP_OK;

@@ -1,7 +1,15 @@
-// api_internal.hpp — shared by the translation units of the C ABI (api.hip: context, model, domain, upload / download, timing; api_rdf.hip: RDF sampling; api_profile.hip: spatial profiles; api_insert.hip: test-particle insertions, Widom sampling;
-// api_step.hip: the pieces of a time step, neighbour lists, ls1hip_run; api_exchange.hip: long-range correction, export / import of
-// the multi-rank exchange, seam A).  Round 4: split out of one 2 400-line api.hip; nothing here is exported from the
-// library (LS1_INTERNAL = hidden visibility).
+// api_internal.hpp — shared by the translation units of the C ABI; nothing here is exported from the library (LS1_INTERNAL = hidden
+// visibility).
+//   api.hip              context, options, model, domain, upload / download, timing
+//   api_step.hip         the pieces of a time step, neighbour lists, ls1hip_run and its sampler table
+//   api_exchange.hip     long-range correction, export / import of the multi-rank exchange, seam A
+//   api_rdf.hip          RDF sampling
+//   api_odf.hip          ODF sampling
+//   api_cavity.hip       cavity detection
+//   api_profile.hip      spatial profiles
+//   api_planar.hip       planar long-range correction
+//   api_insert.hip       test-particle insertions, Widom sampling
+//   api_tempcontrol.hip  region-wise temperature control
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -76,6 +84,29 @@ static inline void timer_free(Timer& t) {
 	t.ev.clear();
 	t.used = 0;
 }
+// every timer of a context: its name in ls1hip_timing; ls1hip_timing_reset and ls1hip_destroy walk the list
+struct TimerName {
+	const char* name;
+	Timer ls1hip_ctx::*t;
+};
+constexpr TimerName TIMERS[] = {
+	{"force", &ls1hip_ctx::t_force},
+	{"integrate", &ls1hip_ctx::t_integrate},
+	{"rebin", &ls1hip_ctx::t_rebin},
+	{"build", &ls1hip_ctx::t_build},
+	{"halo", &ls1hip_ctx::t_halo},
+	{"rdf", &ls1hip_ctx::t_rdf},
+	{"odf", &ls1hip_ctx::t_odf},
+	{"cavity", &ls1hip_ctx::t_cavity},
+	{"profile", &ls1hip_ctx::t_profile},
+	{"insert", &ls1hip_ctx::t_insert},
+	{"planar_density", &ls1hip_ctx::t_pl_density},
+	{"planar_tables", &ls1hip_ctx::t_pl_tables},
+	{"planar_apply", &ls1hip_ctx::t_pl_apply},
+	{"tempcontrol_measure", &ls1hip_ctx::t_tc_measure},
+	{"tempcontrol_betas", &ls1hip_ctx::t_tc_betas},
+	{"tempcontrol_apply", &ls1hip_ctx::t_tc_apply},
+};
 
 // ---- memory helpers ------------------------------------------------------------------------------------------------
 template <class T>
@@ -129,6 +160,54 @@ static inline void free_cells(ls1hip_ctx* c) {
 	c->n_shell = 0;
 }
 
+// ---- what the sampling passes share ---------------------------------------------------------------------------------------------
+// The state a pass over the binned molecules and their halo needs (RDF, ODF, cavities, insertions).  Between two builds of the
+// neighbour lists a drift leaves the binning of the last build in place (stale by at most skin / 2, the grid is sized by r_c + skin):
+// that is what the list force pass walks too.  On multi-rank domains a re-binning in progress (ls1hip_rebin before import_done(0))
+// keeps the lists formally alive, so only a finished binning counts there.
+static inline int sample_gate(ls1hip_ctx* c) {
+	REQUIRE(c, c->binned || (c->vl_ready && !c->has_remote), "molecules are not binned (call ls1hip_rebin)");
+	REQUIRE(c, c->halo_valid, "halo not populated (call ls1hip_halo / import_done(1), or ls1hip_halo_refresh between list builds)");
+	REQUIRE(c, !c->fused_split && !c->inner_in_flight, "a split force pass is in flight");
+	return LS1HIP_OK;
+}
+
+// where the CURRENT positions live (ls1hip_ctx::pos_x)
+struct Pos3 {
+	double *x, *y, *z;
+};
+static inline Pos3 cur_pos(const ls1hip_ctx* c) {
+	const MolSoA& m = c->mol[c->cur];
+	return c->pos_x ? Pos3{c->pos_x, c->pos_y, c->pos_z} : Pos3{m.x, m.y, m.z};
+}
+
+// grid, current positions, orientations, components, cell table and counters of a pass over the cells (ForceParams, InsertParams)
+template <class Params>
+static inline void fill_cell_args(const ls1hip_ctx* c, Params& P) {
+	const MolSoA& m = c->mol[c->cur];
+	const Pos3 r = cur_pos(c);
+	P.g = c->g;
+	P.x = r.x; P.y = r.y; P.z = r.z;
+	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
+	P.cid = m.cid;
+	P.cell_begin = c->d_cell_begin; P.cell_end = c->d_cell_end;
+	P.ct = c->d_ct;
+	P.cnt = c->d_cnt;
+}
+
+// owned molecules per cell of the box: the brick kernels choose their shape by it
+static inline double mean_per_cell(const ls1hip_ctx* c) {
+	const double ncell = (double)c->g.box[0] * c->g.box[1] * c->g.box[2];
+	return ncell > 0 ? (double)c->n_real / ncell : 0.;
+}
+
+// rows of a device ring, oldest first: the last min(written, cap) rows of `row` bytes each, at most two contiguous runs
+static inline int ring_read(ls1hip_ctx* c, const void* ring, size_t row, uint64_t written, size_t cap, void* out) {
+	const size_t have = (size_t)std::min<uint64_t>(written, cap), first = (size_t)((written - have) % cap), n1 = std::min(have, cap - first);
+	if (n1) HIPCHK(c, hipMemcpy(out, (const char*)ring + first * row, n1 * row, hipMemcpyDeviceToHost));
+	if (have > n1) HIPCHK(c, hipMemcpy((char*)out + n1 * row, ring, (have - n1) * row, hipMemcpyDeviceToHost));
+	return LS1HIP_OK;
+}
 
 // ---- helpers defined in one translation unit and used by another ---------------------------------------------------------------
 LS1_INTERNAL bool can_fuse(const ls1hip_ctx* c);

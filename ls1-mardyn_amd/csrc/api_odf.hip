@@ -19,10 +19,7 @@ static void odf_free(ls1hip_ctx* c) {
 	c->odf_samples = 0;
 }
 
-void odf_destroy(ls1hip_ctx* c) {
-	odf_free(c);
-	timer_free(c->t_odf);
-}
+void odf_destroy(ls1hip_ctx* c) { odf_free(c); }
 
 // ODF::readXML + ODF::init (ODF.cpp:6-79)
 extern "C" int ls1hip_odf_config(ls1hip_ctx* c, int phi1_increments, int phi2_increments, int gamma_increments, double shell_cutoff) {
@@ -65,25 +62,16 @@ extern "C" int ls1hip_odf_layout(const ls1hip_ctx* c, size_t* words_per_array) {
 	return LS1HIP_OK;
 }
 
-// one traversal over the current positions and orientations (ODF::afterForces -> traverseCells(ODFCellProcessor), ODF.cpp:81-85);
-// the state rules of rdf_sample_impl
+// one traversal over the current positions and orientations (ODF::afterForces -> traverseCells(ODFCellProcessor), ODF.cpp:81-85)
 int odf_sample_impl(ls1hip_ctx* c) {
 	REQUIRE(c, c->odf_phi > 0 && c->d_odf, "ODF sampling is not configured (ls1hip_odf_config)");
-	REQUIRE(c, c->binned || (c->vl_ready && !c->has_remote), "molecules are not binned (call ls1hip_rebin)");
-	REQUIRE(c, c->halo_valid, "halo not populated (call ls1hip_halo / import_done(1), or ls1hip_halo_refresh between list builds)");
-	REQUIRE(c, !c->fused_split && !c->inner_in_flight, "a split force pass is in flight");
+	if (int rc = sample_gate(c)) return rc;
 	REQUIRE(c, c->g.hw == 1, "ODF sampling serves grids with one cell per cutoff (cells_in_cutoff = 1)");
 	REQUIRE(c, odf_dipole_mask(c) == c->odf_mask, "the component set changed since ls1hip_odf_config");
 	const MolSoA& m = c->mol[c->cur];
 	ForceParams P;
 	memset(&P, 0, sizeof(P));
-	P.g = c->g;
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
-	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
-	P.cid = m.cid;
-	P.cell_begin = c->d_cell_begin; P.cell_end = c->d_cell_end;
-	P.ct = c->d_ct;
-	P.cnt = c->d_cnt;
+	fill_cell_args(c, P);
 	OdfParams O;
 	memset(&O, 0, sizeof(O));
 	O.P = c->odf_phi;
@@ -94,10 +82,9 @@ int odf_sample_impl(ls1hip_ctx* c) {
 	O.id = m.id;
 	O.hsrc = c->d_halo_src;
 	O.g_hist = c->d_odf;
-	const double ncell = (double)c->g.box[0] * c->g.box[1] * c->g.box[2];
 	{
 		TimedScope ts(c, c->t_odf);
-		if (!launch_odf(P, O, c->h_ct.has_rot != 0, ncell > 0 ? (double)c->n_real / ncell : 0., c->stream))
+		if (!launch_odf(P, O, c->h_ct.has_rot != 0, mean_per_cell(c), c->stream))
 			FAIL(c, LS1HIP_EINVAL, "the ODF pass could not be launched for this grid");
 	}
 	HIPCHK(c, hipGetLastError());

@@ -16,12 +16,7 @@ static void planar_free(ls1hip_ctx* c) {
 	c->pl_tables_valid = false;
 }
 
-void planar_destroy(ls1hip_ctx* c) {
-	planar_free(c);
-	timer_free(c->t_pl_density);
-	timer_free(c->t_pl_tables);
-	timer_free(c->t_pl_apply);
-}
+void planar_destroy(ls1hip_ctx* c) { planar_free(c); }
 
 // Planar::init (Planar.cpp:40-157): rows, elongations, muSquare, slab geometry; the ordered pairs of calculateLongRange (:338-371)
 extern "C" int ls1hip_planar_config(ls1hip_ctx* c, int slabs, int frequency, double region_left, double region_right, double temperature) {
@@ -149,7 +144,8 @@ static int planar_params(ls1hip_ctx* c, PlanarParams& P, bool molecules) {
 			"the state was advanced by a fused force + integration pass (the correction follows an unfused force pass)");
 	REQUIRE(c, c->pl.ncomp == c->h_ct.ncomp, "the component set changed since ls1hip_planar_config");
 	const MolSoA& m = c->mol[c->cur];
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
+	const Pos3 r = cur_pos(c);
+	P.x = r.x; P.y = r.y; P.z = r.z;
 	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
 	P.cid = m.cid;
 	P.Fy = c->frc.Fy; P.Mx = c->frc.Mx; P.Mz = c->frc.Mz;
@@ -306,9 +302,5 @@ extern "C" int ls1hip_planar_log(ls1hip_ctx* c, size_t cap_rows, double* rows2, 
 	REQUIRE(c, cap_rows >= have, "buffer too small: %zu < %zu rows", cap_rows, have);
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const size_t first = (c->steplog_steps - have) % STEPLOG_ROWS;
-	const size_t n1 = std::min(have, STEPLOG_ROWS - first);
-	HIPCHK(c, hipMemcpy(rows2, c->d_pl_log + 2 * first, n1 * 2 * sizeof(double), hipMemcpyDeviceToHost));
-	if (have > n1) HIPCHK(c, hipMemcpy(rows2 + 2 * n1, c->d_pl_log, (have - n1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
-	return LS1HIP_OK;
+	return ring_read(c, c->d_pl_log, 2 * sizeof(double), c->steplog_steps, STEPLOG_ROWS, rows2);
 }

@@ -19,10 +19,7 @@ static void prof_free(ls1hip_ctx* c) {
 	c->prof_samples = 0;
 }
 
-void profile_destroy(ls1hip_ctx* c) {
-	prof_free(c);
-	timer_free(c->t_profile);
-}
+void profile_destroy(ls1hip_ctx* c) { prof_free(c); }
 
 // the table layout for the current configuration (ProfParams: offsets in words)
 static void prof_layout(const ls1hip_ctx* c, ProfParams& P) {
@@ -134,7 +131,8 @@ int profile_sample_impl(ls1hip_ctx* c, bool scaled) {
 	} else {
 		for (int d = 0; d < 3; ++d) P.inv[d] = P.units[d] / c->global_len[d];  // SpatialProfile.cpp:181-183
 	}
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
+	const Pos3 r = cur_pos(c);
+	P.x = r.x; P.y = r.y; P.z = r.z;
 	P.vx = m.vx; P.vy = m.vy; P.vz = m.vz;
 	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
 	P.Dx = m.Dx; P.Dy = m.Dy; P.Dz = m.Dz;

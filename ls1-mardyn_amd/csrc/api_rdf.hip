@@ -34,10 +34,7 @@ static void rdf_free(ls1hip_ctx* c) {
 	c->rdf_samples = 0;
 }
 
-void rdf_destroy(ls1hip_ctx* c) {
-	rdf_free(c);
-	timer_free(c->t_rdf);
-}
+void rdf_destroy(ls1hip_ctx* c) { rdf_free(c); }
 
 extern "C" int ls1hip_rdf_config(ls1hip_ctx* c, int bins, double interval_length, int site_rdf) {
 	if (!c) return LS1HIP_EINVAL;
@@ -78,12 +75,7 @@ extern "C" int ls1hip_rdf_layout(const ls1hip_ctx* c, size_t* mol_words, size_t*
 // one traversal over the current positions; the caller has checked nothing
 int rdf_sample_impl(ls1hip_ctx* c) {
 	REQUIRE(c, c->rdf_bins > 0 && c->d_rdf, "RDF sampling is not configured (ls1hip_rdf_config)");
-	// between two builds of the neighbour lists a drift leaves the binning of the last build in place (stale by at most skin / 2, the
-	// grid is sized by r_c + skin): that is what the list force pass walks too.  On multi-rank domains a re-binning in progress
-	// (ls1hip_rebin before import_done(0)) keeps the lists formally alive, so only a finished binning counts there.
-	REQUIRE(c, c->binned || (c->vl_ready && !c->has_remote), "molecules are not binned (call ls1hip_rebin)");
-	REQUIRE(c, c->halo_valid, "halo not populated (call ls1hip_halo / import_done(1), or ls1hip_halo_refresh between list builds)");
-	REQUIRE(c, !c->fused_split && !c->inner_in_flight, "a split force pass is in flight");
+	if (int rc = sample_gate(c)) return rc;
 	REQUIRE(c, c->g.hw == 1, "RDF sampling serves grids with one cell per cutoff (cells_in_cutoff = 1)");
 	RdfParams R;
 	memset(&R, 0, sizeof(R));
@@ -94,13 +86,7 @@ int rdf_sample_impl(ls1hip_ctx* c) {
 	// pos_x may also name the force arrays (after a fused per-step pass), but then the molecules are not binned: refused above
 	ForceParams P;
 	memset(&P, 0, sizeof(P));
-	P.g = c->g;
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
-	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
-	P.cid = m.cid;
-	P.cell_begin = c->d_cell_begin; P.cell_end = c->d_cell_end;
-	P.ct = c->d_ct;
-	P.cnt = c->d_cnt;
+	fill_cell_args(c, P);
 	R.bins = c->rdf_bins;
 	R.ncomp = c->h_ct.ncomp;
 	R.dr = c->rdf_dr;
@@ -114,10 +100,9 @@ int rdf_sample_impl(ls1hip_ctx* c) {
 	R.g_mol = c->d_rdf;
 	R.g_site = c->d_rdf + mw;
 	R.g_n = c->d_rdf + mw + sw;
-	const double ncell = (double)c->g.box[0] * c->g.box[1] * c->g.box[2];
 	{
 		TimedScope ts(c, c->t_rdf);
-		if (!launch_rdf(P, R, c->h_ct.has_rot != 0, ncell > 0 ? (double)c->n_real / ncell : 0., c->stream))
+		if (!launch_rdf(P, R, c->h_ct.has_rot != 0, mean_per_cell(c), c->stream))
 			FAIL(c, LS1HIP_EINVAL, "the RDF pass could not be launched for this grid");
 	}
 	HIPCHK(c, hipGetLastError());

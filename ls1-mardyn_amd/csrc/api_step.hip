@@ -208,8 +208,6 @@ static int launch_forces(ls1hip_ctx* c, const ForcePass& fp) {
 	if (first_pass && c->opt_count_pairs) launch_clear_macro(c->d_cnt, c->stream);
 	bool done = false;
 	int family = LS1HIP_FK_LDS_LIST;
-	const double ncell = (double)c->g.box[0] * c->g.box[1] * c->g.box[2];
-	const double mean_per_cell = ncell > 0 ? (double)c->n_real / ncell : 0.;
 	// local rebuild criterion (kernels_force_verlet.hip, k_bound_local): complete fused traversals of a single periodic domain
 	const bool local_ok = fp.vl && c->one_clj && which == 0 && !c->has_remote && c->opt_local_rebuild && c->d_vl_top2;
 	const bool local_crit = local_ok && fuse;
@@ -230,7 +228,8 @@ static int launch_forces(ls1hip_ctx* c, const ForcePass& fp) {
 			// drift speed per group; post_kick: it does the post-force kick and leaves {sum m v^2, sum I w^2, rot. DOF} per group
 			const MolSoA& ms = c->mol[c->cur];
 			P.Dx = ms.Dx; P.Dy = ms.Dy; P.Dz = ms.Dz;
-			P.ox = c->pos_x ? c->pos_x : ms.x; P.oy = c->pos_x ? c->pos_y : ms.y; P.oz = c->pos_x ? c->pos_z : ms.z;  // (= P.x y z, writable)
+			const Pos3 r = cur_pos(c);
+			P.ox = r.x; P.oy = r.y; P.oz = r.z;  // (= P.x y z, writable)
 			P.oq0 = ms.q0; P.oq1 = ms.q1; P.oq2 = ms.q2; P.oq3 = ms.q3;
 			P.msl_pk_out = c->d_msl_pk2;
 			P.msl_vmax = c->d_partials + (size_t)4 * msl_groups((uint32_t)c->n_real, P.msl_g);  // behind the macroscopic partials
@@ -252,7 +251,7 @@ static int launch_forces(ls1hip_ctx* c, const ForcePass& fp) {
 		family = LS1HIP_FK_NEIGHBOUR_LIST;
 		if (local_crit) launch_bound_local(c->g, c->d_vl_top2, c->d_vl_acc, c->d_cnt, fp.dt, 0.5 * c->vl_skin, c->stream);
 	} else if (c->one_clj && c->opt_force_kernel != LS1HIP_FK_GENERIC && !c->opt_vi && !c->opt_count_pairs) {
-		done = launch_force_lj(P, c->stream, &nblocks, c->d_partials, c->partials_cap, (int)c->opt_lj_split, mean_per_cell,
+		done = launch_force_lj(P, c->stream, &nblocks, c->d_partials, c->partials_cap, (int)c->opt_lj_split, mean_per_cell(c),
 							   &c->brick_lists);
 	} else if (!c->one_clj && c->opt_force_kernel != LS1HIP_FK_GENERIC && !c->opt_count_pairs && which != 3) {
 		double vol = 1.;
@@ -262,13 +261,13 @@ static int launch_forces(ls1hip_ctx* c, const ForcePass& fp) {
 		// by the per-brick staging / search chain, not by the pair bodies, and the site kernel (cheaper bodies, more phases)
 		// measured 10-20 % slower; it is there on request
 		if (c->opt_force_kernel == LS1HIP_FK_MS_SITES) {
-			done = launch_force_sites(P, c->h_ct, c->opt_vi != 0, c->stream, &nblocks, c->partials_cap, mean_per_cell, nbrs,
+			done = launch_force_sites(P, c->h_ct, c->opt_vi != 0, c->stream, &nblocks, c->partials_cap, mean_per_cell(c), nbrs,
 									  &c->brick_lists);
 			if (done) family = LS1HIP_FK_MS_SITES;
 		}
 		if (!done) {
 			done = launch_force_ms(P, c->opt_vi != 0, c->h_ct.has_rot != 0, c->h_ct.ncomp == 1, c->stream, &nblocks, c->partials_cap,
-								   mean_per_cell, &c->brick_lists);
+								   mean_per_cell(c), &c->brick_lists);
 			if (done) family = LS1HIP_FK_MS_BRICK;
 		}
 	}
@@ -754,8 +753,7 @@ static int verlet_build(ls1hip_ctx* c) {
 static int verlet_refresh_halo(ls1hip_ctx* c) {
 	TimedScope ts(c, c->t_halo);
 	HaloArgs a = halo_args(c);
-	const MolSoA& m = c->mol[c->cur];
-	double *x = c->pos_x ? c->pos_x : m.x, *y = c->pos_x ? c->pos_y : m.y, *z = c->pos_x ? c->pos_z : m.z;
+	const auto [x, y, z] = cur_pos(c);
 	launch_halo_refresh(a, x, y, z, x, y, z, c->stream);
 	HIPCHK(c, hipGetLastError());
 	c->halo_valid = true;
@@ -882,8 +880,7 @@ extern "C" int ls1hip_halo_refresh(ls1hip_ctx* c) {
 	TimedScope ts(c, c->t_halo, hs);
 	c->halo_import_at = 0;
 	HaloArgs a = halo_args(c);
-	const MolSoA& m = c->mol[c->cur];
-	double *x = c->pos_x ? c->pos_x : m.x, *y = c->pos_x ? c->pos_y : m.y, *z = c->pos_x ? c->pos_z : m.z;
+	const auto [x, y, z] = cur_pos(c);
 	launch_halo_refresh(a, x, y, z, x, y, z, hs);
 	if (c->has_remote) {
 		launch_refresh_pack(a, x, y, z, c->d_exp_refresh, hs);
@@ -998,15 +995,62 @@ extern "C" int ls1hip_update(ls1hip_ctx* c, int* rebuilt) {
 	return LS1HIP_OK;
 }
 
+// ---- the passes ls1hip_run samples with: one row each -----------------------------------------------------------------------------
+// A pass is due on the steps with simstep % every == 0 from its first step on.  All but the profiles read the positions of the step's
+// force evaluation and nothing else: they run directly BEFORE the force pass (a fused pass leaves the next step's positions behind),
+// on the refreshed or regenerated halo, in the order of the rows; nothing of the step itself changes.  The profiles sample the state
+// at the END of the step (before_forces = nullptr: ls1hip_run calls them itself).
+struct Sampler {
+	const char* stem;  // option "<stem>_every"
+	long ls1hip_ctx::*every;
+	long ls1hip_ctx::*from;  // first step (nullptr: none)
+	bool after_from;         // the first step is excluded: simstep > from, not >=
+	bool (*configured)(const ls1hip_ctx*);
+	const char* unconfigured;  // completes "option <stem>_every is set but ..."
+	int (*before_forces)(ls1hip_ctx*);
+};
+static const Sampler SAMPLERS[] = {
+	// RDF::afterForces (RDF.cpp:573-581): simstep % samplingfrequency == 0
+	{"rdf", &ls1hip_ctx::opt_rdf_every, nullptr, false, [](const ls1hip_ctx* c) { return c->rdf_bins > 0; },
+	 "RDF sampling is not configured (ls1hip_rdf_config)", rdf_sample_impl},
+	// ODF::afterForces (ODF.cpp:81-85): simstep > _initStatistics && simstep % _recordingTimesteps == 0
+	{"odf", &ls1hip_ctx::opt_odf_every, &ls1hip_ctx::opt_odf_from, true, [](const ls1hip_ctx* c) { return c->odf_phi > 0; },
+	 "ODF sampling is not configured (ls1hip_odf_config)", odf_sample_impl},
+	// CavityWriter::afterForces (CavityWriter.cpp:160-174): simstep >= getInitStatistics() && simstep % _writeFrequency == 0
+	{"cavity", &ls1hip_ctx::opt_cavity_every, &ls1hip_ctx::opt_cavity_from, false, [](const ls1hip_ctx* c) { return c->d_cav_flags != nullptr; },
+	 "cavity detection is not configured (ls1hip_cavity_config)", cavity_sample_impl},
+	// SpatialProfile::endStep (SpatialProfile.cpp:238): simstep >= _initStatistics && simstep % _profileRecordingTimesteps == 0
+	// samples the state at the END of the step — full-step velocities, after the thermostat.  Such a step goes the unfused way
+	// (as the last one does): force pass, post-force kick, sampling pass; the head of the next step then only drifts.
+	{"profile", &ls1hip_ctx::opt_profile_every, &ls1hip_ctx::opt_profile_from, false, [](const ls1hip_ctx* c) { return c->prof_bins > 0; },
+	 "profile sampling is not configured (ls1hip_profile_config)", nullptr},
+	// Widom test insertions: the step counting of the RDF
+	{"widom", &ls1hip_ctx::opt_widom_every, nullptr, false, [](const ls1hip_ctx* c) { return c->wd.n > 0; },
+	 "Widom sampling is not configured (ls1hip_widom_config)", widom_sample_impl},
+};
+static const Sampler& PROFILES = SAMPLERS[3];
+
+static bool sample_due(const ls1hip_ctx* c, const Sampler& r, unsigned long simstep) {
+	const unsigned long every = (unsigned long)(c->*r.every), from = r.from ? (unsigned long)(c->*r.from) : 0;
+	return every > 0 && (r.after_from ? simstep > from : simstep >= from) && simstep % every == 0;
+}
+static bool any_due_before_forces(const ls1hip_ctx* c, unsigned long simstep) {
+	for (const Sampler& r : SAMPLERS)
+		if (r.before_forces && sample_due(c, r, simstep)) return true;
+	return false;
+}
+static int run_samples_before_forces(ls1hip_ctx* c, unsigned long simstep) {
+	for (const Sampler& r : SAMPLERS)
+		if (r.before_forces && sample_due(c, r, simstep))
+			if (int rc = r.before_forces(c)) return rc;
+	return LS1HIP_OK;
+}
+
 extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double* out6) {
 	if (!c) return LS1HIP_EINVAL;
 	REQUIRE(c, !c->has_remote, "ls1hip_run drives single-rank domains only (use the piecewise calls with a transport)");
 	REQUIRE(c, c->forces_valid, "initial forces required (rebin, halo, forces) before ls1hip_run");
-	REQUIRE(c, !c->opt_rdf_every || c->rdf_bins > 0, "option rdf_every is set but RDF sampling is not configured (ls1hip_rdf_config)");
-	REQUIRE(c, !c->opt_odf_every || c->odf_phi > 0, "option odf_every is set but ODF sampling is not configured (ls1hip_odf_config)");
-	REQUIRE(c, !c->opt_cavity_every || c->d_cav_flags, "option cavity_every is set but cavity detection is not configured (ls1hip_cavity_config)");
-	REQUIRE(c, !c->opt_profile_every || c->prof_bins > 0, "option profile_every is set but profile sampling is not configured (ls1hip_profile_config)");
-	REQUIRE(c, !c->opt_widom_every || c->wd.n > 0, "option widom_every is set but Widom sampling is not configured (ls1hip_widom_config)");
+	for (const Sampler& r : SAMPLERS) REQUIRE(c, !(c->*r.every) || r.configured(c), "option %s_every is set but %s", r.stem, r.unconfigured);
 	HIPCHK(c, hipSetDevice(c->device));
 	// Between two steps of an NVE run on the LJ fast path the force pass does the integration itself (fused mode, the
 	// reference's reduced-memory scheme); the last step is unfused so that F and the kinetic sums are available.
@@ -1068,43 +1112,22 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		}
 		kicked = false;
 		const unsigned long simstep = ++c->run_step;
-		// SpatialProfile::endStep (SpatialProfile.cpp:238): simstep >= _initStatistics && simstep % _profileRecordingTimesteps == 0
-		// samples the state at the END of the step — full-step velocities, after the thermostat.  Such a step goes the unfused way
-		// (as the last one does): force pass, post-force kick, sampling pass; the head of the next step then only drifts.
-		const bool prof_now = c->opt_profile_every > 0 && simstep >= (unsigned long)c->opt_profile_from &&
-							  simstep % (unsigned long)c->opt_profile_every == 0;
+		const bool prof_now = sample_due(c, PROFILES, simstep);
 		advanced = fuse && s + 1 < nsteps && !prof_now;
-		// RDF::afterForces (RDF.cpp:573-581): simstep % samplingfrequency == 0 samples the positions of this step's force evaluation.
-		// The pass runs directly BEFORE the force pass (a fused pass leaves the next step's positions behind), on the refreshed
-		// or regenerated halo; nothing of the step itself changes.
-		const bool rdf_now = c->opt_rdf_every > 0 && simstep % (unsigned long)c->opt_rdf_every == 0;
-		// ODF::afterForces (ODF.cpp:81-85): simstep > _initStatistics && simstep % _recordingTimesteps == 0; same place, the pass only reads
-		const bool odf_now = c->opt_odf_every > 0 && simstep > (unsigned long)c->opt_odf_from && simstep % (unsigned long)c->opt_odf_every == 0;
-		// CavityWriter::afterForces (CavityWriter.cpp:160-174): simstep >= getInitStatistics() && simstep % _writeFrequency == 0 counts on
-		// the positions of this step's force evaluation; same place (behind a fused pass they would be gone), the pass only reads
-		const bool cavity_now = c->opt_cavity_every > 0 && simstep >= (unsigned long)c->opt_cavity_from && simstep % (unsigned long)c->opt_cavity_every == 0;
-		// Widom test insertions: same place, same step counting; the pass only reads
-		const bool widom_now = c->opt_widom_every > 0 && simstep % (unsigned long)c->opt_widom_every == 0;
 		if (verlet) {
 			// the lists, the binning and the halo slots live until the displacement bound of the molecules (accumulated on
 			// the device by whichever pass drifts them) exceeds skin / 2; then re-bin, regenerate the halo, rebuild the lists
 			if ((rc = ls1hip_update(c, nullptr))) return rc;
-			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
-			if (odf_now && (rc = odf_sample_impl(c))) return rc;
-			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
-			if (widom_now && (rc = widom_sample_impl(c))) return rc;
+			if ((rc = run_samples_before_forces(c, simstep))) return rc;
 			// unfused steps (the last one; every step of an NVT run): the pass still does the post-force kick + sum m v^2
 			rc = advanced ? ls1hip_forces_list(c, 0, dt, nullptr, nullptr)
 						  : forces_list_impl(c, 0, list_kick ? dt : 0., list_kick, nullptr, nullptr);
-		} else if (c->opt_overlap_halo == 2 || (c->opt_overlap_halo && (rdf_now || odf_now || cavity_now || widom_now))) {
+		} else if (c->opt_overlap_halo == 2 || (c->opt_overlap_halo && any_due_before_forces(c, simstep))) {
 			if ((rc = ls1hip_rebin(c))) return rc;
 			// halo first, then the inner and the boundary cells as two passes of the same stream (also the order of a sampling
 			// step of mode 1: the RDF pass needs the halo before the first force pass moves anything)
 			if ((rc = ls1hip_halo(c))) return rc;
-			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
-			if (odf_now && (rc = odf_sample_impl(c))) return rc;
-			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
-			if (widom_now && (rc = widom_sample_impl(c))) return rc;
+			if ((rc = run_samples_before_forces(c, simstep))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 1, dt, nullptr, nullptr) : ls1hip_forces(c, 1, nullptr, nullptr);
 			if (rc) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 2, dt, nullptr, nullptr) : ls1hip_forces(c, 2, nullptr, nullptr);
@@ -1118,10 +1141,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		} else {
 			if ((rc = ls1hip_rebin(c))) return rc;
 			if ((rc = ls1hip_halo(c))) return rc;
-			if (rdf_now && (rc = rdf_sample_impl(c))) return rc;
-			if (odf_now && (rc = odf_sample_impl(c))) return rc;
-			if (cavity_now && (rc = cavity_sample_impl(c))) return rc;
-			if (widom_now && (rc = widom_sample_impl(c))) return rc;
+			if ((rc = run_samples_before_forces(c, simstep))) return rc;
 			rc = advanced ? ls1hip_forces_kick_drift(c, 0, dt, nullptr, nullptr) : ls1hip_forces(c, 0, nullptr, nullptr);
 		}
 		if (rc) return rc;
@@ -1181,11 +1201,6 @@ extern "C" int ls1hip_run_log(ls1hip_ctx* c, size_t cap_rows, double* rows, size
 	REQUIRE(c, cap_rows >= have, "buffer too small: %zu < %zu rows", cap_rows, have);
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	// oldest row first: the log is a ring over the step number (at most two contiguous runs)
-	const size_t first = (c->steplog_steps - have) % STEPLOG_ROWS;
-	const size_t n1 = std::min(have, STEPLOG_ROWS - first);
-	HIPCHK(c, hipMemcpy(rows, c->d_steplog + 6 * first, n1 * 6 * sizeof(double), hipMemcpyDeviceToHost));
-	if (have > n1) HIPCHK(c, hipMemcpy(rows + 6 * n1, c->d_steplog, (have - n1) * 6 * sizeof(double), hipMemcpyDeviceToHost));
-	return LS1HIP_OK;
+	return ring_read(c, c->d_steplog, 6 * sizeof(double), c->steplog_steps, STEPLOG_ROWS, rows);  // a ring over the step number
 }
 

@@ -18,12 +18,7 @@ static void tc_free(ls1hip_ctx* c) {
 	for (auto& k : c->tc_configs) k = 0;
 }
 
-void tempcontrol_destroy(ls1hip_ctx* c) {
-	tc_free(c);
-	timer_free(c->t_tc_measure);
-	timer_free(c->t_tc_betas);
-	timer_free(c->t_tc_apply);
-}
+void tempcontrol_destroy(ls1hip_ctx* c) { tc_free(c); }
 
 // TemperatureControl::readXML, control/* (TemperatureControl.cpp:579-586)
 extern "C" int ls1hip_tempcontrol_config(ls1hip_ctx* c, unsigned long start, unsigned long frequency, unsigned long stop) {
@@ -111,7 +106,8 @@ static int tc_check_state(ls1hip_ctx* c) {
 TcParams tempcontrol_params(ls1hip_ctx* c) {
 	const MolSoA& m = c->mol[c->cur];
 	TcParams P = c->tc;
-	P.x = c->pos_x ? c->pos_x : m.x; P.y = c->pos_x ? c->pos_y : m.y; P.z = c->pos_x ? c->pos_z : m.z;
+	const Pos3 r = cur_pos(c);
+	P.x = r.x; P.y = r.y; P.z = r.z;
 	P.vx = m.vx; P.vy = m.vy; P.vz = m.vz;
 	P.q0 = m.q0; P.q1 = m.q1; P.q2 = m.q2; P.q3 = m.q3;
 	P.Dx = m.Dx; P.Dy = m.Dy; P.Dz = m.Dz;

@@ -1,4 +1,5 @@
-// brick.hpp — helpers shared by the brick-tiled force kernels (kernels_force_lj.hip, kernels_force_ms.hip).
+// brick.hpp — helpers shared by the brick-tiled kernels: the force kernels (kernels_force_*.hip) and the sampling passes
+// (kernels_rdf.hip, kernels_odf.hip).
 #pragma once
 #include "common.hpp"
 
@@ -107,6 +108,89 @@ __device__ __forceinline__ void brick_region_table(const ForceParams& P, const B
 		gbeg[c] = beg;
 		cstart[c] = n;
 	}
+}
+
+// ---- prologue and launcher of the sampling passes (k_rdf_brick, k_odf_brick) ------------------------------------------------------------
+// The force kernels (kernels_force_*.hip) carry copies of the same prologue.  They are the benchmarked hot path and keep their
+// own text on purpose: the copies are known.
+
+// Region cell table and its prefix (cstart[0..NRC], gbeg), prefix of the brick's own cells (bstart[0..NBC]); total: molecules of the
+// region, n_i: owned molecules of the brick.  All threads must call.
+template <int NT, int HW, int BX, int BY, int BZ>
+__device__ __forceinline__ void brick_prefixes(const ForceParams& P, const BrickSel& bs, uint32_t* cstart, uint32_t* gbeg, uint32_t* bstart,
+												uint32_t* wsum, uint32_t& total, uint32_t& n_i) {
+	constexpr int RX = BX + 2 * HW, RY = BY + 2 * HW, RZ = BZ + 2 * HW;
+	constexpr int NRC = RX * RY * RZ, NBC = BX * BY * BZ;
+	static_assert(NRC <= NT * 4 && NBC <= NT * 4, "region too large for the block scan");
+	brick_region_table<NT, HW, RX, RY, RZ>(P, bs, cstart, gbeg);
+	__syncthreads();
+	block_scan_lds<NT>(cstart, NRC, wsum);
+	total = cstart[NRC];
+	for (int c = threadIdx.x; c < NBC; c += NT) {
+		const int cx = c % BX, cy = (c / BX) % BY, cz = c / (BX * BY);
+		uint32_t n = 0;
+		if (cx < bs.ex && cy < bs.ey && cz < bs.ez) {
+			const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
+			n = cstart[rcell + 1] - cstart[rcell];
+		}
+		bstart[c] = n;
+	}
+	__syncthreads();
+	block_scan_lds<NT>(bstart, NBC, wsum);
+	n_i = bstart[NBC];
+}
+
+// the cell of slot s: the last c in [0, n) with prefix[c] <= s
+__device__ __forceinline__ int slot_cell(const uint32_t* prefix, int n, uint32_t s) {
+	int lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const int mid = (lo + hi) >> 1;
+		if (prefix[mid] <= s) lo = mid;
+		else hi = mid;
+	}
+	return lo;
+}
+
+// slot that holds the quaternion of slot g: a halo image takes it from its source molecule — between two builds of the neighbour
+// lists only the POSITIONS of the halo copies are refreshed (ls1hip_halo_refresh), the owned molecules' orientations are always current
+__device__ __forceinline__ uint32_t halo_source_slot(uint32_t g, uint32_t n_real, const uint32_t* hsrc) {
+	if (g >= n_real) {
+		const uint32_t s = hsrc[g - n_real];
+		if (s != 0xffffffffu) return s;
+	}
+	return g;
+}
+
+// owned molecule number `it` of the brick: its staging slot, its global index, the first cell of row 0 of its neighbourhood
+struct BrickOwned {
+	uint32_t ii, gi;
+	int rowbase;
+};
+template <int HW, int BX, int BY, int BZ>
+__device__ __forceinline__ BrickOwned brick_owned(const uint32_t* cstart, const uint32_t* gbeg, const uint32_t* bstart, uint32_t it) {
+	constexpr int RX = BX + 2 * HW, RY = BY + 2 * HW;
+	const int lo = slot_cell(bstart, BX * BY * BZ, it);
+	const int cx = lo % BX, cy = (lo / BX) % BY, cz = lo / (BX * BY);
+	const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
+	const uint32_t k = it - bstart[lo];
+	return {cstart[rcell] + k, gbeg[rcell] + k, (cz * RY + cy) * RX + cx};
+}
+
+// launch of a sampling pass over ALL bricks of shape BX x BY x BZ: bricks per dimension, the pass selection of p cleared; returns the
+// grid size (a multiple of 8: the XCD-aware order of brick_select), 0 when the grid cannot be launched
+template <int BX, int BY, int BZ>
+static inline uint32_t all_bricks_grid(ForceParams& p, int& nbx, int& nby, int& nbz) {
+	const Grid& g = p.g;
+	nbx = (g.box[0] + BX - 1) / BX, nby = (g.box[1] + BY - 1) / BY, nbz = (g.box[2] + BZ - 1) / BZ;
+	const long nb = (long)nbx * nby * nbz;
+	if (nb <= 0 || nb > 0x7ffffff0L) return 0;
+	p.which = 0;
+	p.brick_list = nullptr;
+	p.n_list = 0;
+	p.inner_box = 0;
+	p.did_mode = 0;
+	p.brick_did = nullptr;
+	return (uint32_t)(8 * ((nb + 7) / 8));
 }
 
 // number of workgroups of a brick traversal (multiple of 8 for the XCD-aware order); fills p.brick_list / p.n_list for

@@ -95,6 +95,22 @@ __device__ __forceinline__ double wave_fold_max(double v) {
 	v = fmax(v, wave_down_f64<1>(v));
 	return v;
 }
+// number of lanes below the calling one whose bit is set in the ballot m
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// orders the LDS accesses of ONE wave (table / queue writes of some lanes, reads by others): LDS instructions of a wave execute in
+// order, only the compiler must not move them
+__device__ __forceinline__ void wave_lds_order() {
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// rotation of a quaternion as stored: FullMolecule::setupSoACache normalises before rotating
+__device__ __forceinline__ Rot rot_of_stored(double w, double x, double y, double z) {
+	const double inv = 1. / sqrt(w * w + x * x + y * y + z * z);
+	return rot_of(w * inv, x * inv, y * inv, z * inv);
+}
 
 // The 64-byte per-step record of the multi-site pair-stream force pass (kernels_force_mslist.hip): {x, y, z, component id, q0, q1,
 // q2, q3 (normalised once per molecule and step: FullMolecule::setupSoACache normalises q before rotating, FullMolecule.cpp:720)}.  Written by k_msl_pack and by the rigid-body kick + drift passes (IntegArgs::pk) — ONE body, contraction off, so that the

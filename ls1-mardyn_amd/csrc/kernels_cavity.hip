@@ -51,10 +51,6 @@ constexpr int CAV_CHECK = 8;     // survivors between two "is this wave decided"
 
 size_t cavity_chunk_max() { return (size_t)CAV_CAP; }
 
-__device__ __forceinline__ uint32_t cav_lanes_below(uint64_t m) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 // the series word of this sample: cleared by a kernel of its own (no memset node, should a caller ever capture the pass)
 __global__ void k_cavity_clear(unsigned long long* w) { *w = 0ull; }
 
@@ -149,7 +145,7 @@ __global__ void __launch_bounds__(CTPB) k_cavity(CavityParams P) {
 					if ((int)lane == leader) b = atomicAdd(&fill[par], (uint32_t)__popcll(m));
 					b = __shfl(b, leader);
 					if (keep) {
-						const uint32_t k = b + cav_lanes_below(m);  // < e - s <= CAV_CAP
+						const uint32_t k = b + lanes_below(m);  // < e - s <= CAV_CAP
 						const uint64_t id = P.id[g];
 						sr[3 * k] = x; sr[3 * k + 1] = y; sr[3 * k + 2] = z;
 						sid[k] = id >> 32 ? 0u : (uint32_t)id;

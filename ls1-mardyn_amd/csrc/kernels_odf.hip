@@ -105,7 +105,6 @@ __global__ void __launch_bounds__(OTPB) k_odf_brick(ForceParams P, OdfParams O, 
 	constexpr int NRC = RX * RY * RZ;
 	constexpr int NBC = BX * BY * BZ;
 	constexpr int NW = 3, NROWS = 9;
-	static_assert(NRC <= NT * 4 && NBC <= NT * 4, "region too large for the block scan");
 	__shared__ double sx[CAPJ], sy[CAPJ], sz[CAPJ];
 	__shared__ double ox[CAPJ], oy[CAPJ], oz[CAPJ];  // orientation vector e
 	__shared__ uint64_t sid[CAPJ];
@@ -121,27 +120,12 @@ __global__ void __launch_bounds__(OTPB) k_odf_brick(ForceParams P, OdfParams O, 
 	const int tid = threadIdx.x;
 	const BrickSel bs = brick_select<HW, BX, BY, BZ>(P, nbx, nby, nbz);
 	if (!bs.live) return;  // uniform per workgroup
-	const int ex = bs.ex, ey = bs.ey, ez = bs.ez;
 	const uint32_t W = O.W, lds_words = O.hist_lds ? 4u * W : 0u;  // <= ODF_LDS_WORDS (launch_odf)
 	for (uint32_t w = tid; w < lds_words; w += NT) hist[w] = 0u;
 	if (tid < 3) qc[tid] = 0u;
 	// ---- region cell table, brick cell prefix --------------------------------------------------------------------------
-	brick_region_table<NT, HW, RX, RY, RZ>(P, bs, cstart, gbeg);
-	__syncthreads();
-	block_scan_lds<NT>(cstart, NRC, wsum);
-	const uint32_t total = cstart[NRC];
-	for (int c = tid; c < NBC; c += NT) {
-		const int cx = c % BX, cy = (c / BX) % BY, cz = c / (BX * BY);
-		uint32_t n = 0;
-		if (cx < ex && cy < ey && cz < ez) {
-			const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
-			n = cstart[rcell + 1] - cstart[rcell];
-		}
-		bstart[c] = n;
-	}
-	__syncthreads();
-	block_scan_lds<NT>(bstart, NBC, wsum);
-	const uint32_t n_i = bstart[NBC];
+	uint32_t total, n_i;
+	brick_prefixes<NT, HW, BX, BY, BZ>(P, bs, cstart, gbeg, bstart, wsum, total, n_i);
 	const bool staged = total <= (uint32_t)CAPJ;
 	const uint32_t n_real = P.cnt->n_real;
 	const uint32_t mask = O.dip_mask;
@@ -150,21 +134,13 @@ __global__ void __launch_bounds__(OTPB) k_odf_brick(ForceParams P, OdfParams O, 
 	auto evec = [&](uint32_t g, double& vx, double& vy, double& vz) {
 		vx = 0.; vy = 0.; vz = 1.;
 		if (!has_rot) return;  // (no component has a dipole then: nothing is marked)
-		if (g >= n_real) {
-			const uint32_t s = O.hsrc[g - n_real];
-			if (s != 0xffffffffu) g = s;
-		}
+		g = halo_source_slot(g, n_real, O.hsrc);
 		odf_evec(P.q0[g], P.q1[g], P.q2[g], P.q3[g], vx, vy, vz);
 	};
 	auto comp_byte = [&](int c) { return ((mask >> c) & 1u) ? (uint8_t)c : ODF_NOT_DIPOLAR; };
 	if (staged) {
 		for (uint32_t s = tid; s < total; s += NT) {
-			int lo = 0, hi = NRC;
-			while (hi - lo > 1) {
-				const int mid = (lo + hi) >> 1;
-				if (cstart[mid] <= s) lo = mid;
-				else hi = mid;
-			}
+			const int lo = slot_cell(cstart, NRC, s);
 			const uint32_t g = gbeg[lo] + (s - cstart[lo]);
 			sx[s] = P.x[g];
 			sy[s] = P.y[g];
@@ -204,18 +180,8 @@ __global__ void __launch_bounds__(OTPB) k_odf_brick(ForceParams P, OdfParams O, 
 		uint32_t ii = 0, gi = 0;
 		int rowbase = 0;
 		if (act) {
-			int lo = 0, hi = NBC;
-			while (hi - lo > 1) {
-				const int mid = (lo + hi) >> 1;
-				if (bstart[mid] <= it) lo = mid;
-				else hi = mid;
-			}
-			const int cx = lo % BX, cy = (lo / BX) % BY, cz = lo / (BX * BY);
-			const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
-			const uint32_t k = it - bstart[lo];
-			ii = cstart[rcell] + k;
-			gi = gbeg[rcell] + k;
-			rowbase = (cz * RY + cy) * RX + cx;  // first cell of row 0 of the neighbourhood
+			const BrickOwned o = brick_owned<HW, BX, BY, BZ>(cstart, gbeg, bstart, it);
+			ii = o.ii; gi = o.gi; rowbase = o.rowbase;
 		}
 		if (staged) {
 			act = act && scid[ii] != ODF_NOT_DIPOLAR;
@@ -305,17 +271,9 @@ __global__ void __launch_bounds__(OTPB) k_odf_brick(ForceParams P, OdfParams O, 
 
 template <int BX, int BY, int BZ>
 static bool launch_odf_shape(ForceParams p, const OdfParams& o, bool has_rot, hipStream_t s) {
-	const Grid& g = p.g;
-	const int nbx = (g.box[0] + BX - 1) / BX, nby = (g.box[1] + BY - 1) / BY, nbz = (g.box[2] + BZ - 1) / BZ;
-	const long nb = (long)nbx * nby * nbz;
-	if (nb <= 0 || nb > 0x7ffffff0L) return false;
-	p.which = 0;
-	p.brick_list = nullptr;
-	p.n_list = 0;
-	p.inner_box = 0;
-	p.did_mode = 0;
-	p.brick_did = nullptr;
-	const dim3 grid((uint32_t)(8 * ((nb + 7) / 8))), block(OTPB);  // multiple of 8: the XCD-aware order of brick_select
+	int nbx, nby, nbz;
+	const dim3 grid(all_bricks_grid<BX, BY, BZ>(p, nbx, nby, nbz)), block(OTPB);
+	if (!grid.x) return false;
 	hipLaunchKernelGGL((k_odf_brick<BX, BY, BZ>), grid, block, 0, s, p, o, has_rot ? 1 : 0, nbx, nby, nbz);
 	return true;
 }

@@ -42,11 +42,6 @@ __device__ __forceinline__ V3 rdf_site_pos(const CompTable& ct, int c, int m) {
 	return ld3(ct.qppos, ct.oq[c] + m);
 }
 
-__device__ __forceinline__ Rot rdf_rot(double w, double x, double y, double z) {
-	const double inv = 1. / sqrt(w * w + x * x + y * y + z * z);  // FullMolecule::setupSoACache normalises before rotating
-	return rot_of(w * inv, x * inv, y * inv, z * inv);
-}
-
 template <int BX, int BY, int BZ, int CAPJ, int CAPL, bool SITE>
 __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, const CompTable* __restrict__ ctab, int has_rot, int nbx,
 												   int nby, int nbz) {
@@ -56,7 +51,6 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 	constexpr int NBC = BX * BY * BZ;
 	constexpr int NW = 3, NROWS = 9;
 	constexpr int QN = SITE ? CAPJ : 1;
-	static_assert(NRC <= NT * 4 && NBC <= NT * 4, "region too large for the block scan");
 	__shared__ double sx[CAPJ], sy[CAPJ], sz[CAPJ];
 	__shared__ double sq0[QN], sq1[QN], sq2[QN], sq3[QN];  // quaternion as stored (normalised when the rotation is formed)
 	__shared__ uint64_t sid[CAPJ];
@@ -72,47 +66,18 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 	const int tid = threadIdx.x;
 	const BrickSel bs = brick_select<HW, BX, BY, BZ>(P, nbx, nby, nbz);
 	if (!bs.live) return;  // uniform per workgroup
-	const int ex = bs.ex, ey = bs.ey, ez = bs.ez;
 	const uint32_t mol_base = 0, site_base = R.mol_lds ? R.mol_words : 0u;
 	const uint32_t lds_words = (R.mol_lds ? R.mol_words : 0u) + ((SITE && R.site_lds) ? R.site_words : 0u);  // <= RDF_LDS_WORDS (launch_rdf)
 	for (uint32_t w = tid; w < lds_words; w += NT) hist[w] = 0u;
 	if (tid < MAXC) ncnt[tid] = 0u;
 	// ---- region cell table, brick cell prefix --------------------------------------------------------------------------
-	brick_region_table<NT, HW, RX, RY, RZ>(P, bs, cstart, gbeg);
-	__syncthreads();
-	block_scan_lds<NT>(cstart, NRC, wsum);
-	const uint32_t total = cstart[NRC];
-	for (int c = tid; c < NBC; c += NT) {
-		const int cx = c % BX, cy = (c / BX) % BY, cz = c / (BX * BY);
-		uint32_t n = 0;
-		if (cx < ex && cy < ey && cz < ez) {
-			const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
-			n = cstart[rcell + 1] - cstart[rcell];
-		}
-		bstart[c] = n;
-	}
-	__syncthreads();
-	block_scan_lds<NT>(bstart, NBC, wsum);
-	const uint32_t n_i = bstart[NBC];
+	uint32_t total, n_i;
+	brick_prefixes<NT, HW, BX, BY, BZ>(P, bs, cstart, gbeg, bstart, wsum, total, n_i);
 	const bool staged = total <= (uint32_t)CAPJ;
 	const uint32_t n_real = P.cnt->n_real;
-	// quaternion of slot g: a halo image takes it from its source molecule — between two builds of the neighbour lists only the
-	// POSITIONS of the halo copies are refreshed (ls1hip_halo_refresh), the owned molecules' orientations are always current
-	auto qslot = [&](uint32_t g) {
-		if (g >= n_real) {
-			const uint32_t s = R.hsrc[g - n_real];
-			if (s != 0xffffffffu) return s;
-		}
-		return g;
-	};
 	if (staged) {
 		for (uint32_t s = tid; s < total; s += NT) {
-			int lo = 0, hi = NRC;
-			while (hi - lo > 1) {
-				const int mid = (lo + hi) >> 1;
-				if (cstart[mid] <= s) lo = mid;
-				else hi = mid;
-			}
+			const int lo = slot_cell(cstart, NRC, s);
 			const uint32_t g = gbeg[lo] + (s - cstart[lo]);
 			sx[s] = P.x[g];
 			sy[s] = P.y[g];
@@ -122,7 +87,7 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 			if (SITE) {
 				double w = 1., x = 0., y = 0., z = 0.;
 				if (has_rot) {
-					const uint32_t gq = qslot(g);
+					const uint32_t gq = halo_source_slot(g, n_real, R.hsrc);
 					w = P.q0[gq]; x = P.q1[gq]; y = P.q2[gq]; z = P.q3[gq];
 				}
 				sq0[s] = w; sq1[s] = x; sq2[s] = y; sq3[s] = z;
@@ -155,7 +120,7 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 			if (off == 0xffffffffu) return;
 			const int ni = R.nsites[ci], nj = R.nsites[cj];
 			const uint32_t nb = (uint32_t)R.nsites[cb];
-			const Rot Rj = has_rot ? rdf_rot(jq0, jq1, jq2, jq3) : rot_of(1., 0., 0., 0.);
+			const Rot Rj = has_rot ? rot_of_stored(jq0, jq1, jq2, jq3) : rot_of(1., 0., 0., 0.);
 			for (int m = 0; m < ni; ++m) {
 				const V3 pi = ri + rotate(Ri, rdf_site_pos(*ctab, ci, m));
 				for (int n = 0; n < nj; ++n) {
@@ -177,23 +142,12 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 	for (uint32_t base = 0; base < n_i; base += NT) {  // one pass unless the brick holds more than 256 molecules
 		const uint32_t it = base + (uint32_t)tid;
 		if (it >= n_i) continue;
-		int lo = 0, hi = NBC;
-		while (hi - lo > 1) {
-			const int mid = (lo + hi) >> 1;
-			if (bstart[mid] <= it) lo = mid;
-			else hi = mid;
-		}
-		const int cx = lo % BX, cy = (lo / BX) % BY, cz = lo / (BX * BY);
-		const int rcell = ((cz + HW) * RY + (cy + HW)) * RX + (cx + HW);
-		const uint32_t k = it - bstart[lo];
-		const uint32_t ii = cstart[rcell] + k;
-		const uint32_t gi = gbeg[rcell] + k;
-		const int rowbase = (cz * RY + cy) * RX + cx;  // first cell of row 0 of the neighbourhood
+		const auto [ii, gi, rowbase] = brick_owned<HW, BX, BY, BZ>(cstart, gbeg, bstart, it);
 		if (staged) {
 			const V3 ri = {sx[ii], sy[ii], sz[ii]};
 			const int ci = (int)scid[ii];
 			const uint64_t idi = sid[ii];
-			const Rot Ri = (SITE && has_rot) ? rdf_rot(sq0[ii], sq1[ii], sq2[ii], sq3[ii]) : rot_of(1., 0., 0., 0.);
+			const Rot Ri = (SITE && has_rot) ? rot_of_stored(sq0[ii], sq1[ii], sq2[ii], sq3[ii]) : rot_of(1., 0., 0., 0.);
 			atomicAdd(&ncnt[ci], 1u);
 			// Phase 1 / phase 2 in windows of CAPL hits, as k_force_ms_brick: the walk over the 9 neighbour rows appends the hits
 			// number [done, done + CAPL) branch-free to the per-lane list; the binning (IEEE sqrt and division, LDS atomics, the
@@ -233,7 +187,7 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 			const int ci = P.cid[gi];
 			const uint64_t idi = R.id[gi];
 			Rot Ri = rot_of(1., 0., 0., 0.);
-			if (SITE && has_rot) Ri = rdf_rot(P.q0[gi], P.q1[gi], P.q2[gi], P.q3[gi]);  // (gi is owned)
+			if (SITE && has_rot) Ri = rot_of_stored(P.q0[gi], P.q1[gi], P.q2[gi], P.q3[gi]);  // (gi is owned)
 			atomicAdd(&ncnt[ci], 1u);
 			for (int row = 0; row < NROWS; ++row) {
 				const int r0 = rowbase + (row / NW) * (RY * RX) + (row % NW) * RX;
@@ -245,7 +199,7 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 						const double dd = dx * dx + dy * dy + dz * dz;
 						if (!((dd < rc2) & (idi < R.id[j]))) continue;
 						if (SITE && has_rot) {
-							const uint32_t jq = qslot(j);
+							const uint32_t jq = halo_source_slot(j, n_real, R.hsrc);
 							observe(dd, ci, ri, Ri, P.cid[j], rj, P.q0[jq], P.q1[jq], P.q2[jq], P.q3[jq]);
 						} else {
 							observe(dd, ci, ri, Ri, P.cid[j], rj, 1., 0., 0., 0.);
@@ -268,17 +222,9 @@ __global__ void __launch_bounds__(RTPB) k_rdf_brick(ForceParams P, RdfParams R, 
 
 template <int BX, int BY, int BZ>
 static bool launch_rdf_shape(ForceParams p, const RdfParams& r, bool site, bool has_rot, hipStream_t s) {
-	const Grid& g = p.g;
-	const int nbx = (g.box[0] + BX - 1) / BX, nby = (g.box[1] + BY - 1) / BY, nbz = (g.box[2] + BZ - 1) / BZ;
-	const long nb = (long)nbx * nby * nbz;
-	if (nb <= 0 || nb > 0x7ffffff0L) return false;
-	p.which = 0;
-	p.brick_list = nullptr;
-	p.n_list = 0;
-	p.inner_box = 0;
-	p.did_mode = 0;
-	p.brick_did = nullptr;
-	const dim3 grid((uint32_t)(8 * ((nb + 7) / 8))), block(RTPB);  // multiple of 8: the XCD-aware order of brick_select
+	int nbx, nby, nbz;
+	const dim3 grid(all_bricks_grid<BX, BY, BZ>(p, nbx, nby, nbz)), block(RTPB);
+	if (!grid.x) return false;
 	if (site) hipLaunchKernelGGL((k_rdf_brick<BX, BY, BZ, 600, 31, true>), grid, block, 0, s, p, r, p.ct, has_rot ? 1 : 0, nbx, nby, nbz);
 	else hipLaunchKernelGGL((k_rdf_brick<BX, BY, BZ, 1312, 47, false>), grid, block, 0, s, p, r, p.ct, 0, nbx, nby, nbz);
 	return true;
