@@ -536,6 +536,45 @@ int ls1hip_planar_read(ls1hip_ctx* ctx, int layout[3], size_t cap, double* rho, 
  * rows2 [nrows][2], oldest first, as ls1hip_run_log. */
 int ls1hip_planar_log(ls1hip_ctx* ctx, size_t cap_rows, double* rows2, size_t* nrows);
 
+/* ---- external walls: LJ 9-3 / 10-4-3 wall potential, mirrors -----------------------------------------------------------------
+ * What closes the reference's film, adsorption and evaporation set-ups in y: plugins/WallPotential.{h,cpp} (an integrated Lennard-Jones
+ * wall felt by every LJ site, hook siteWiseForces) and plugins/Mirror.{h,cpp} (a reflecting plane or a harmonic restoring force, hook
+ * afterForces).  Both act between the force pass and the kick, so they are ONE device pass over the owned molecules (kernels_wall.hip)
+ * that reads y alone of every molecule out of reach and leaves its F, M and v bit for bit.  Positions are global coordinates, so every
+ * rank of a decomposed run applies the pass to its own molecules.  The wall's energy, Sum over sites of (u - u_shift) per component, has
+ * an output of its own: the reference keeps it in Domain::setLocalUpotCompSpecific only, it is part of neither U_pot nor the virial.
+ * DEVIATION: the 10-4-3 energy and its shift are computed with 2./5.; the reference's integer 2 / 5 is 0 (WallPotential.cpp:184, 318)
+ * and nothing it writes shows that energy.  Forces are the reference's expressions as written.
+ * Not served: the deprecated mirror types 3 and 4, MT_MELAND_2004 (5) and MT_RAMPING (6) — they delete molecules and draw random numbers —,
+ * mirror positions tracked by DistControl (position/refID != 0), more than 4 mirrors, the wall's halo molecules in the energy sum (the
+ * reference iterates ALL_CELLS; the device sums owned molecules). */
+/* WallPotential::readXML + initializeLJ93 / initializeLJ1043 (WallPotential.cpp:10-187).  potential: 0 off, 93, 104 (anything else is
+ * refused; the reference falls back to 9-3); density, sigma, epsilon: the wall's; yoff, ycut, width, delta as in the XML (delta is read
+ * by the 10-4-3 form only).  ncomp must be the component count; consider[c] != 0: component c feels the wall (NULL: every component,
+ * the XML without <component> entries); xi, eta: [ncomp] (read for the considered components).  eps_wi, sig_wi and the energy shift come
+ * from LJ centre 0 of the component: a considered component without an LJ centre is LS1HIP_EINVAL (the reference reads ljcenter(0) of
+ * nothing).  Needs components and domain.  The mirrors are kept. */
+int ls1hip_wall_config(ls1hip_ctx* ctx, int potential, double density, double sigma, double epsilon, double yoff, double ycut, double width,
+                       double delta, int ncomp, const int* consider, const double* xi, const double* eta);
+/* Mirror::readXML (Mirror.cpp:53-187) of one of 4 mirrors.  slot 0..3; type 0 off, 1 MT_REFLECT, 2 MT_FORCE_CONSTANT (3..6:
+ * LS1HIP_EINVAL with a message, see above); direction 0 left |-o (the mirror owns y < coord and sends molecules to the right), 1 right
+ * o-| (y >= coord); coord = position/coord with refID 0; cid 0 = every component, else the 1-based component id of the XML;
+ * force_constant: read by type 2. */
+int ls1hip_mirror_config(ls1hip_ctx* ctx, int slot, int type, int direction, double coord, int cid, double force_constant);
+/* The pass on the current F and v: calcTSLJ_9_3 / calcTSLJ_10_4 (WallPotential.cpp:193-341), then Mirror::VelocityChange of every
+ * mirror in slot order (Mirror.cpp:421-477; membership by the half-open test of MoleculeInterface::inBox on the wrapped centre).
+ * Hosts call it after a force pass, as they call ls1hip_long_range_planar; it needs valid forces and is refused after a fused force +
+ * integration pass.  upot_comp: [ncomp] wall energy per component of this rank's molecules, or NULL.
+ * The reference's driver does NOT apply the wall to the initial forces (siteWiseForces returns at simstep 0, prepare_start does not call
+ * it) but it DOES call the mirrors there (Simulation.cpp:880-886): a host that reproduces it calls this once on the initial state
+ * with the mirrors configured and the wall not (yet).  Timer "wall". */
+int ls1hip_wall_apply(ls1hip_ctx* ctx, double* upot_comp);
+/* Inside ls1hip_run a configured wall or mirror is applied after every force pass (after the planar correction: the reference runs
+ * wall, correction, mirror — Simulation.cpp:1041-1079 — which differs in the rounding order of the additions to F only); fused passes
+ * and the list pass's own kick are off, as with the planar correction.  The per-component energies of every step go to a device ring
+ * beside the step log; rows [nrows][ncomp], oldest first, as ls1hip_run_log; nrows = 0 if the last ls1hip_run had neither a wall nor a mirror. */
+int ls1hip_wall_log(ls1hip_ctx* ctx, size_t cap_rows, double* rows, size_t* nrows);
+
 /* ---- test-particle insertions, Widom sampling -----------------------------------------------------------------
  * The energy a molecule WOULD have at a point, without adding it: what ChemicalPotential::grandcanonicalStep
  * (ensemble/ChemicalPotential.cpp:451-591) asks LinkedCells::getEnergy for, once per ghost molecule

@@ -98,6 +98,11 @@ SYMBOLS = {
     "ls1hip_planar_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ls1hip_planar_read": (C.c_int, [C.c_void_p, _ip, C.c_size_t, _dp, _dp, _dp, _dp, _dp]),
     "ls1hip_planar_log": (C.c_int, [C.c_void_p, C.c_size_t, _dp, C.POINTER(C.c_size_t)]),
+    "ls1hip_wall_config": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_int, _ip, _dp, _dp]),
+    "ls1hip_mirror_config": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double]),
+    "ls1hip_wall_apply": (C.c_int, [C.c_void_p, _dp]),
+    "ls1hip_wall_log": (C.c_int, [C.c_void_p, C.c_size_t, _dp, C.POINTER(C.c_size_t)]),
     "ls1hip_insertion_energies": (C.c_int, [C.c_void_p, C.c_size_t, _i32p, _dp, _dp, _u64p, _dp]),
     "ls1hip_widom_config": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_double, C.c_uint64, C.c_int, _dp, _dp]),
     "ls1hip_widom_sample": (C.c_int, [C.c_void_p]),

@@ -66,6 +66,7 @@ extern "C" int ls1hip_destroy(ls1hip_ctx* c) {
 	cavity_destroy(c);
 	profile_destroy(c);
 	planar_destroy(c);
+	wall_destroy(c);
 	insert_destroy(c);
 	tempcontrol_destroy(c);
 	if (c->d_ingest) hipFree(c->d_ingest);

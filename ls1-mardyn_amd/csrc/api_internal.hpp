@@ -8,6 +8,7 @@
 //   api_cavity.hip       cavity detection
 //   api_profile.hip      spatial profiles
 //   api_planar.hip       planar long-range correction
+//   api_wall.hip         wall potential, mirrors
 //   api_insert.hip       test-particle insertions, Widom sampling
 //   api_tempcontrol.hip  region-wise temperature control
 #pragma once
@@ -103,6 +104,7 @@ constexpr TimerName TIMERS[] = {
 	{"planar_density", &ls1hip_ctx::t_pl_density},
 	{"planar_tables", &ls1hip_ctx::t_pl_tables},
 	{"planar_apply", &ls1hip_ctx::t_pl_apply},
+	{"wall", &ls1hip_ctx::t_wall},
 	{"tempcontrol_measure", &ls1hip_ctx::t_tc_measure},
 	{"tempcontrol_betas", &ls1hip_ctx::t_tc_betas},
 	{"tempcontrol_apply", &ls1hip_ctx::t_tc_apply},
@@ -235,6 +237,11 @@ LS1_INTERNAL void profile_destroy(ls1hip_ctx* c);
 // row that also receives {Upot_c, Virial_c}
 LS1_INTERNAL int planar_impl(ls1hip_ctx* c, double* log2);
 LS1_INTERNAL void planar_destroy(ls1hip_ctx* c);
+// api_wall.hip: the wall + mirror pass (ls1hip_wall_apply; ls1hip_run with a wall or a mirror configured); log: ring row that also
+// receives the per-component energies
+LS1_INTERNAL bool wall_active(const ls1hip_ctx* c);
+LS1_INTERNAL int wall_impl(ls1hip_ctx* c, double* log);
+LS1_INTERNAL void wall_destroy(ls1hip_ctx* c);
 // api_insert.hip: one Widom sample (ls1hip_widom_sample; ls1hip_run with "widom_every")
 LS1_INTERNAL int widom_sample_impl(ls1hip_ctx* c);
 LS1_INTERNAL void insert_destroy(ls1hip_ctx* c);

@@ -1057,16 +1057,19 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 	// With the planar long-range correction configured every step goes the unfused route NVT and sampling steps take: a force pass that
 	// leaves F, then Planar::calculateLongRange (Simulation.cpp:1048-1049: before the forces are used), then the kicks.
 	const bool planar = c->pl.slabs > 0;
+	// A wall or a mirror (WallPotential::siteWiseForces, Mirror::afterForces: Simulation.cpp:1041-1046, 1075-1080) acts in the same
+	// window, so it forces the same route: the forces must exist before anything kicks.  One pass, after the planar correction.
+	const bool ext = wall_active(c);
 	// Region-wise temperature control (Simulation.cpp:1137-1140: after the post-force kick and calculateGlobalValues): every step goes
 	// the unfused route as well; on a control step the measure sweep and the beta kernel follow the post-force kick, the scaling is
 	// folded into the next step's kick + drift (standalone after the last step and before a profile sampling pass)
 	const bool tc = c->tc_frequency > 0 && c->tc.nreg > 0;
 	REQUIRE(c, !(tc && c->thermostat_on), "temperature control and the device thermostat exclude each other");
-	const bool fuse = !planar && !tc && c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
+	const bool fuse = !planar && !ext && !tc && c->opt_fuse && (can_fuse(c) || (can_verlet(c) && can_list_ms(c) && can_fuse_ms(c)));
 	// neighbour-list loop (fused or not: NVT and unfused NVE steps advance the displacement bound in their kick + drift pass)
 	const bool verlet = can_verlet(c) && can_list(c);
 	// the single-centre list pass does the post-force kick (+ sum m v^2) itself; the multi-site one leaves it to the integrator passes
-	const bool list_kick = !planar && verlet && (c->one_clj || (can_list_ms(c) && can_list_kick_ms(c)));
+	const bool list_kick = !planar && !ext && verlet && (c->one_clj || (can_list_ms(c) && can_list_kick_ms(c)));
 	bool advanced = false;  // the previous force pass already did kick + kick + drift
 	bool kicked = false;    // the previous step sampled profiles: its post-force kick (+ kinetic sums, betas) is done
 	// step log: one row {U_pot, virial, sum m v^2, sum I w^2, N, rotDOF} per step, written by the reductions on the device
@@ -1080,6 +1083,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		~LogGuard() { c->log_row = c->log_row_kin = nullptr; }
 	} log_guard{c};
 	c->steplog_steps = 0;
+	c->wl_log_steps = 0;
 	for (unsigned long s = 0; s < nsteps; ++s) {
 		int rc;
 		c->log_row = c->d_steplog + (s % STEPLOG_ROWS) * 6;                         // forces of step s
@@ -1146,6 +1150,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		}
 		if (rc) return rc;
 		if (planar && (rc = planar_impl(c, c->d_pl_log + (s % STEPLOG_ROWS) * 2))) return rc;
+		if (ext && (rc = wall_impl(c, c->d_wl_log + (s % STEPLOG_ROWS) * MAXC))) return rc;
 		if (s + 1 == nsteps || prof_now) {
 			c->log_row_kin = c->log_row;
 			if (!list_kick && (rc = ls1hip_kick(c, 0.5 * dt, nullptr, nullptr, nullptr, nullptr))) return rc;
@@ -1181,6 +1186,7 @@ extern "C" int ls1hip_run(ls1hip_ctx* c, double dt, unsigned long nsteps, double
 		c->pos_x = c->pos_y = c->pos_z = nullptr;
 	}
 	c->steplog_steps = nsteps;
+	c->wl_log_steps = ext ? nsteps : 0;  // (ls1hip_wall_log: rows of THIS run only)
 	int rc = sync_counters(c);
 	if (rc) return rc;
 	if (out6) {

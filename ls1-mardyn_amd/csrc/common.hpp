@@ -112,6 +112,18 @@ __device__ __forceinline__ Rot rot_of_stored(double w, double x, double y, doubl
 	return rot_of(w * inv, x * inv, y * inv, z * inv);
 }
 
+// y wrapped into [0, L) as the profile pass wraps it: the planar and the wall pass (a molecule may sit up to skin / 2 outside between two list builds)
+__device__ __forceinline__ double pl_wrap(double y, double len) {
+	if (y < 0.) {
+		y += len;
+		if (y >= len) y = nextafter(len, 0.);
+	} else if (y >= len) {
+		y -= len;
+		if (y <= 0.) y = 0.;
+	}
+	return y;
+}
+
 // The 64-byte per-step record of the multi-site pair-stream force pass (kernels_force_mslist.hip): {x, y, z, component id, q0, q1,
 // q2, q3 (normalised once per molecule and step: FullMolecule::setupSoACache normalises q before rotating, FullMolecule.cpp:720)}.  Written by k_msl_pack and by the rigid-body kick + drift passes (IntegArgs::pk) — ONE body, contraction off, so that the
 // record is the same bits whichever pass wrote it.
@@ -331,6 +343,39 @@ void launch_planar_density(const PlanarParams& p, bool has_rot, uint32_t n_cap, 
 void launch_planar_tables(const PlanarParams& p, hipStream_t s);
 uint32_t planar_apply_blocks(uint32_t n_cap);
 void launch_planar_apply(const PlanarParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
+
+// external walls (kernels_wall.hip): plugins/WallPotential.cpp (LJ 9-3 / 10-4-3 wall in y) and plugins/Mirror.cpp (reflecting plane,
+// harmonic restoring force), one pass over the owned molecules
+constexpr int WL_MIRRORS = 4;
+constexpr int WL_OFF = 0, WL_93 = 93, WL_104 = 104;                  // WallPotential: potential
+constexpr int WL_MT_OFF = 0, WL_MT_REFLECT = 1, WL_MT_FORCE = 2;     // Mirror: MT_REFLECT, MT_FORCE_CONSTANT
+struct WallComp {  // per component, computed once at configuration as WallPotential::initializeLJ93 / initializeLJ1043 do
+	// 9-3:  pref = 4 pi rho eps_wi sig3_wi, a = sig3_wi, b = sig9_wi;   10-4-3: pref = 2 pi eps_wi rho sig2_wi delta, a = sig4_wi, b = sig10_wi
+	double pref, a, b, ushift;
+	int consider, centre;  // _bConsiderComponent; centre: one LJ site at the centre of mass (no rotation, no torque)
+};
+struct WallMirror {
+	int type, dir, cid;  // WL_MT_*; 0 left |-o, 1 right o-|; 0 = every component, else 1-based
+	double coord, k;     // _position.coord, _forceConstant
+};
+struct WallParams {
+	int potential, ncomp;  // WL_OFF: mirrors only
+	double yoff, whalf, ycut, delta3;  // _yOff, _dWidthHalf, _yc, 3 _delta
+	double delta061;                   // 0.61 _delta
+	double reach[2];                   // centres that can own a site in reach: yoff -+ (width / 2 + ycut + d_max)
+	double len_y;
+	WallMirror mir[WL_MIRRORS];
+	const WallComp* comp;  // [MAXC], device memory (staged in LDS by the workgroups that reach the wall)
+	const double *y, *q0, *q1, *q2, *q3;
+	const int32_t* cid;
+	double *Fy, *Mx, *Mz, *vy;
+	const CompTable* ct;
+	const DevCounters* cnt;
+	double* partials;  // [workgroups][MAXC]
+	double *out, *log;  // [MAXC] per-component wall energy of the last pass; ring row of ls1hip_run (or null)
+};
+uint32_t wall_apply_blocks(uint32_t n_cap);
+void launch_wall_apply(const WallParams& p, bool has_rot, uint32_t n_cap, hipStream_t s);
 
 // test-particle insertions (kernels_insert.hip): ChemicalPotential::grandcanonicalStep -> LinkedCells::getEnergy
 struct InsertParams {
@@ -577,6 +622,14 @@ struct ls1hip_ctx {
 	size_t pl_partials_cap = 0;
 	double* d_pl_log = nullptr;  // ring {Upot_c, Virial_c} beside the step log
 	ls1::Timer t_pl_density, t_pl_tables, t_pl_apply;
+	// external walls (ls1hip_wall_*, ls1hip_mirror_config; kernels_wall.hip): wl holds the wall (potential = 0: off) and the mirrors
+	ls1::WallParams wl{};
+	ls1::WallComp* d_wl_comp = nullptr;  // [MAXC]
+	double *d_wl_partials = nullptr, *d_wl_out = nullptr;
+	size_t wl_partials_cap = 0;
+	double* d_wl_log = nullptr;  // ring [MAXC] per step beside the step log
+	size_t wl_log_steps = 0;     // rows the last ls1hip_run wrote to it (0: it ran without a wall or a mirror)
+	ls1::Timer t_wall;
 	// test-particle insertions (ls1hip_insertion_energies, ls1hip_widom_*; kernels_insert.hip)
 	char* d_ins = nullptr;  // staging of ls1hip_insertion_energies: {r, q, dU, exclude_id, cid} of ins_cap tests
 	size_t ins_cap = 0;

@@ -28,17 +28,7 @@ constexpr int PL_K_LDS = 4096;         // tables: doubles of the two K blocks (2
 constexpr uint32_t PL_TAB_LDS = 6144;  // apply: doubles of the four tables kept in LDS (48 KB)
 uint32_t planar_apply_blocks(uint32_t n_cap) { return (n_cap + PL_PER_WG - 1) / PL_PER_WG; }
 
-// y wrapped into [0, L) as the profile pass wraps it (a molecule may sit up to skin / 2 outside between two list builds)
-__device__ __forceinline__ double pl_wrap(double y, double len) {
-	if (y < 0.) {
-		y += len;
-		if (y >= len) y = nextafter(len, 0.);
-	} else if (y >= len) {
-		y -= len;
-		if (y <= 0.) y = 0.;
-	}
-	return y;
-}
+// (pl_wrap, the y wrap of every pass here: common.hpp — the wall pass shares it)
 // slab of an LJ site (Planar.cpp:285-291): C truncation, one-slab wrap; clamped so that no index leaves the row
 __device__ __forceinline__ int pl_site_slab(const PlanarParams& P, double y) {
 	int loc = (int)(y * P.delta_inv);

@@ -583,6 +583,24 @@ def planar_collect(engine, dist=None, group=None, device=None):
     return engine.planar_counts(t.cpu().numpy().astype(np.uint64))
 
 
+def wall_collect(local, dist=None, group=None, device=None):
+    """The wall energy per component of the whole domain: every rank applies the pass to its own molecules (positions are global
+    coordinates, so no rank needs anything from another) and `local` is what its engine.wall_apply() returned; ONE all-reduce sums
+    them (the reference keeps the value rank-local, in Domain::setLocalUpotCompSpecific).  Without an initialised process group: local."""
+    local = np.asarray(local, dtype=np.float64)
+    if dist is None:
+        import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    import torch
+
+    t = torch.from_numpy(local.copy())
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    return t.cpu().numpy()
+
+
 def tempcontrol_collect(engine, dist=None, group=None, device=None):
     """The collective of ControlRegionT::CalcGlobalValues (thermostats/TemperatureControl.cpp:240-264) on the device's slab sums of
     all regions: ONE all-reduce of a [4, slabs] float64 tensor {n, rotDOF, ekinRot, ekinTrans}.  Call between engine.tempcontrol_measure() and engine.tempcontrol_betas(); returns the global sums, which are then on the device.

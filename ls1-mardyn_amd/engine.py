@@ -529,6 +529,36 @@ class DeviceEngine:
             self._chk(self.lib.ls1hip_planar_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
         return out
 
+    # -- external walls (ls1hip_wall_*, ls1hip_mirror_config: the reference's plugins WallPotential and Mirror) ---------------------
+    def wall_config(self, potential: int, density=0.0, sigma=0.0, epsilon=0.0, yoff=0.0, ycut=0.0, width=0.0, delta=0.0,
+                    consider=None, xi=None, eta=None):
+        """potential 0 (off) | 93 | 104; consider / xi / eta: per component (consider None: every component)."""
+        ncomp = len(self.n_sites)
+        cons = None if consider is None else np.ascontiguousarray(consider, dtype=np.int32)
+        xi = capi.f64(np.zeros(ncomp) if xi is None else xi, (ncomp,))
+        eta = capi.f64(np.zeros(ncomp) if eta is None else eta, (ncomp,))
+        self._chk(self.lib.ls1hip_wall_config(self.ctx, int(potential), float(density), float(sigma), float(epsilon), float(yoff), float(ycut),
+                                              float(width), float(delta), ncomp, capi.iptr(cons), capi.dptr(xi), capi.dptr(eta)))
+
+    def mirror_config(self, slot: int, type: int, direction: int = 0, coord: float = 0.0, cid: int = 0, force_constant: float = 100.0):  # noqa: A002
+        """type 0 off | 1 reflect | 2 force constant; direction 0 left |-o | 1 right o-|; cid 0 all, else 1-based."""
+        self._chk(self.lib.ls1hip_mirror_config(self.ctx, int(slot), int(type), int(direction), float(coord), int(cid), float(force_constant)))
+
+    def wall_apply(self):
+        """The wall + mirror pass on the current F and v; returns the wall energy per component [ncomp] of this rank's molecules."""
+        out = np.zeros(max(len(self.n_sites), 1))
+        self._chk(self.lib.ls1hip_wall_apply(self.ctx, capi.dptr(out)))
+        return out[:len(self.n_sites)]
+
+    def wall_log(self):
+        """[nsteps, ncomp] wall energy per component of every step of the last run."""
+        n = C.c_size_t()
+        self._chk(self.lib.ls1hip_wall_log(self.ctx, 0, None, C.byref(n)))
+        out = np.zeros((n.value, len(self.n_sites)))
+        if n.value:
+            self._chk(self.lib.ls1hip_wall_log(self.ctx, n.value, capi.dptr(out), C.byref(n)))
+        return out
+
     # -- region-wise temperature control (ls1hip_tempcontrol_*: the reference's thermostats/TemperatureControl) --------------------
     def tempcontrol_config(self, start: int, frequency: int, stop: int):
         """control/start, frequency, stop; frequency = 0 removes the thermostat and its regions."""

@@ -609,6 +609,70 @@ class Planar:
         return path
 
 
+class WallPotential:
+    """The reference's plugin WallPotential (plugins/WallPotential.{h,cpp}) over the device pass: the XML's parameters by their names —
+    potential (93 | 104), density, sigma, epsilon, yoff, ycut, width, delta — and components = {cid (1-based, the XML's @id): (xi, eta)}.
+    As in readXML (:43-75) an empty `components` makes EVERY component feel the wall, with xi = eta = 0 (so with no force)."""
+
+    def __init__(self, potential: int = 93, density: float = 1.0, sigma: float = 1.0, epsilon: float = 1.0, yoff: float = 0.0,
+                 ycut: float = 1.0, width: float = 0.0, delta: float = 0.0, components=None):
+        if int(potential) not in (93, 104):
+            raise ValueError(f"potential must be 93 or 104, got {potential} (the reference falls back to 93 with a log line)")
+        self.potential, self.density, self.sigma, self.epsilon = int(potential), float(density), float(sigma), float(epsilon)
+        self.yoff, self.ycut, self.width, self.delta = float(yoff), float(ycut), float(width), float(delta)
+        self.components = {int(k): (float(xi), float(eta)) for k, (xi, eta) in (components or {}).items()}
+        self._engine = None
+
+    def arrays(self, ncomp: int):
+        """consider [ncomp], xi [ncomp], eta [ncomp] as ls1hip_wall_config takes them"""
+        consider = np.ones(ncomp, dtype=np.int32) if not self.components else np.zeros(ncomp, dtype=np.int32)
+        xi, eta = np.zeros(ncomp), np.zeros(ncomp)
+        for k, (x, e) in self.components.items():
+            if not 1 <= k <= ncomp:
+                raise ValueError(f"component id {k} outside 1..{ncomp}")
+            consider[k - 1], xi[k - 1], eta[k - 1] = 1, x, e
+        return consider, xi, eta
+
+    def init(self, engine):
+        engine.wall_config(self.potential, self.density, self.sigma, self.epsilon, self.yoff, self.ycut, self.width, self.delta,
+                           *self.arrays(len(engine.n_sites)))
+        self._engine = engine
+
+    def siteWiseForces(self, simstep: int = 1):
+        """one pass on the engine's current forces (wall AND configured mirrors: they share the pass); nothing at simstep 0 (:354)"""
+        return None if simstep == 0 else self._engine.wall_apply()
+
+
+class Mirror:
+    """The reference's plugin Mirror (plugins/Mirror.{h,cpp}), types MT_REFLECT (1) and MT_FORCE_CONSTANT (2): type, dir ('|-o' left,
+    'o-|' right) or direction (0 | 1), coord (position/coord), refID (position/refID), cid (0 all, else 1-based), forceConstant.
+    slot: which of the device's 4 mirrors this one is."""
+    REFUSED = {3: "MT_ZERO_GRADIENT is deprecated", 4: "MT_NORMDISTR_MB is deprecated",
+               5: "MT_MELAND_2004 deletes molecules and draws random numbers", 6: "MT_RAMPING deletes molecules and draws random numbers"}
+
+    def __init__(self, type: int = 1, dir: str | None = None, direction: int = 0, coord: float = 0.0, refID: int = 0, cid: int = 0,  # noqa: A002
+                 forceConstant: float = 100.0, slot: int = 0):
+        if int(type) in self.REFUSED:
+            raise NotImplementedError(f"mirror type {type}: {self.REFUSED[int(type)]}; not applied on the device")
+        if int(type) not in (1, 2):
+            raise ValueError(f"mirror type must be 1 (MT_REFLECT) or 2 (MT_FORCE_CONSTANT), got {type}")
+        if int(refID) != 0:
+            raise NotImplementedError("position/refID != 0 (a position tracked by DistControl) is not served on the device")
+        if dir is not None and dir not in ("|-o", "o-|"):
+            raise ValueError(f"dir must be '|-o' or 'o-|', got {dir!r}")
+        self.type, self.cid, self.coord, self.forceConstant, self.slot = int(type), int(cid), float(coord), float(forceConstant), int(slot)
+        self.direction = int(direction) if dir is None else int(dir == "o-|")  # (@dir overrides <direction>, Mirror.cpp:94-102)
+        self._engine = None
+
+    def init(self, engine):
+        engine.mirror_config(self.slot, self.type, self.direction, self.coord, self.cid, self.forceConstant)
+        self._engine = engine
+
+    def afterForces(self):
+        """one pass on the engine's current forces and velocities (every configured mirror AND a configured wall: they share the pass)"""
+        return self._engine.wall_apply()
+
+
 class TemperatureControl:
     """The reference's region-wise thermostat (thermostats/TemperatureControl.{h,cpp}, method VelocityScaling) over the device passes:
     readXML-style arguments (control start / frequency / stop; per region a dict with lc, uc ('box' allowed per coordinate),

@@ -24,13 +24,15 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
 from profile_time import line, one_call  # noqa: E402
 
 
-def film_engine(torch, bench, inp, synth, engine_mod, n):
+def film_engine(torch, bench, inp, synth, engine_mod, n, skin=None):
     L = synth.box_length(n, bench.RHO)
     dev = torch.device("cuda", 0)
     keep = lambda r: (r.view(-1, 3)[:, 1] >= L / 4) & (r.view(-1, 3)[:, 1] < 3 * L / 4)  # noqa: E731
     total = sum(int(keep(r_t).sum()) for _, r_t, _ in synth.bcc_chunks_device(torch, dev, n, rho=bench.RHO, temp=bench.TEMP))
     e = engine_mod.DeviceEngine(0)
     e.set_components(bench.lj_components(inp), bench.RC)
+    if skin:
+        e.set_verlet(skin)
     e.set_domain([L, L, L])
     e.upload_begin(total)
     for ids_t, r_t, v_t in synth.bcc_chunks_device(torch, dev, n, rho=bench.RHO, temp=bench.TEMP):
