@@ -363,6 +363,24 @@ int ls1hip_rdf_read(ls1hip_ctx* ctx, uint64_t* mol, size_t cap_mol, uint64_t* si
 					uint64_t* samples);
 /* RDF::reset (RDF.cpp:309-340): histograms, molecule counters and sample counter back to zero. */
 int ls1hip_rdf_reset(ls1hip_ctx* ctx);
+/* The angular RDF of the same plugin (<angularbins> > 1: io/RDF.h:93-109 observeARDFMolecule, adapter/RDFCellProcessor.cpp:36-41,
+ * MoleculeInterface.h:167-190 orientationAngle, RDF.cpp:49-55, 88-91, 137-146, 253-272, 377-453).  Every pair the RDF pass observes
+ * adds two counts, ardf[c_i][c_j][flat(b, a_ij)] and ardf[c_j][c_i][flat(b, a_ji)]: b the distance bin, a = floor((-cos phi + 1.) /
+ * (2. / angularbins)) with cos phi between the CENTRAL molecule's orientation vector (from its quaternion as stored; (0, 0, 1) for
+ * components without rotation) and the direction to the other one.  The first index is the component of the central molecule: the
+ * nC x nC blocks are not symmetric.  flat = b angularbins + a in signed arithmetic, as the reference's flat index (RDF.h:97-100):
+ * a = -1 (cos phi rounded above 1) or a = angularbins (cos phi <= -1) lands in the neighbouring distance row; only a flat index
+ * outside [0, bins angularbins), where the reference writes outside its vector, is dropped.
+ *
+ * ls1hip_rdf_config_angular: after ls1hip_rdf_config (an error without it).  angularbins <= 1 switches the angular part off and
+ *   frees it; nC^2 bins angularbins words must fit the 32-bit word index.  ls1hip_rdf_config drops the angular configuration (the
+ *   bins changed).  With the angular part on, ls1hip_rdf_sample (and "rdf_every") fills these words in the same sample: one
+ *   traversal for molecule histogram, counters and ARDF without site histograms, a second one behind the RDF pass with them; the
+ *   sample counter ticks once; ls1hip_rdf_reset zeroes them too.  With it off nothing changes. */
+int ls1hip_rdf_config_angular(ls1hip_ctx* ctx, int angularbins);
+/* LOCAL counts of this rank (RDF::collectRDF sums them over the ranks, RDF.cpp:253-272), layout [c_central][c_other][b angularbins
+ * + a]; *words = nC^2 bins angularbins; ardf may be NULL to query *words only.  An error while the angular part is off. */
+int ls1hip_rdf_angular_read(ls1hip_ctx* ctx, uint64_t* ardf, size_t cap, size_t* words);
 /* Option "rdf_every" (ls1hip_set_option, default 0 = never): ls1hip_run samples on every step s with s % rdf_every == 0, s counted
  * from 1 over all ls1hip_run calls of the context (simstep % _samplingFrequency of RDF::afterForces).  The pass runs on the
  * positions of that step's force evaluation, directly before the force pass, on the step's regenerated or refreshed halo; the

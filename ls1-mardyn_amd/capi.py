@@ -75,6 +75,8 @@ SYMBOLS = {
     "ls1hip_rdf_sample": (C.c_int, [C.c_void_p]),
     "ls1hip_rdf_read": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, _u64p, C.c_size_t, _u64p, _u64p]),
     "ls1hip_rdf_reset": (C.c_int, [C.c_void_p]),
+    "ls1hip_rdf_config_angular": (C.c_int, [C.c_void_p, C.c_int]),
+    "ls1hip_rdf_angular_read": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ls1hip_odf_config": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]),
     "ls1hip_odf_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "ls1hip_odf_sample": (C.c_int, [C.c_void_p]),

@@ -25,7 +25,14 @@ static void rdf_words(const ls1hip_ctx* c, int bins, int site_rdf, size_t* mol, 
 	*site = sw;
 }
 
+static void ardf_free(ls1hip_ctx* c) {
+	dfree(c->d_ardf);
+	c->ardf_abins = 0;
+	c->ardf_words = 0;
+}
+
 static void rdf_free(ls1hip_ctx* c) {
+	ardf_free(c);  // its rows are the distance bins
 	dfree(c->d_rdf);
 	c->rdf_bins = 0;
 	c->rdf_site = 0;
@@ -65,6 +72,23 @@ extern "C" int ls1hip_rdf_config(ls1hip_ctx* c, int bins, double interval_length
 	return LS1HIP_OK;
 }
 
+extern "C" int ls1hip_rdf_config_angular(ls1hip_ctx* c, int angularbins) {
+	if (!c) return LS1HIP_EINVAL;
+	HIPCHK(c, hipSetDevice(c->device));
+	REQUIRE(c, c->rdf_bins > 0 && c->d_rdf, "RDF sampling is not configured (ls1hip_rdf_config comes first)");
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	ardf_free(c);
+	if (angularbins <= 1) return LS1HIP_OK;  // RDF.cpp:49-56: _doARDF = false
+	const size_t nc = (size_t)c->h_ct.ncomp, pair = (size_t)c->rdf_bins * (size_t)angularbins, words = nc * nc * pair;
+	REQUIRE(c, words < (size_t)0x7fffffff, "angular histograms of %zu words exceed the 32-bit word index", words);
+	int rc = dalloc(c, &c->d_ardf, words);
+	if (rc) return rc;
+	HIPCHK(c, hipMemsetAsync(c->d_ardf, 0, words * sizeof(unsigned long long), c->stream));
+	c->ardf_abins = angularbins;
+	c->ardf_words = words;
+	return LS1HIP_OK;
+}
+
 extern "C" int ls1hip_rdf_layout(const ls1hip_ctx* c, size_t* mol_words, size_t* site_words) {
 	if (!c) return LS1HIP_EINVAL;
 	if (mol_words) *mol_words = c->rdf_mol_words;
@@ -100,10 +124,27 @@ int rdf_sample_impl(ls1hip_ctx* c) {
 	R.g_mol = c->d_rdf;
 	R.g_site = c->d_rdf + mw;
 	R.g_n = c->d_rdf + mw + sw;
+	// the angular part: without site histograms ONE traversal bins molecule histogram, counters and ARDF (k_ardf_brick, MOL); with
+	// them k_rdf_brick runs as ever and the ARDF words come from a second traversal
+	const bool ang = c->ardf_abins > 1;
+	ArdfParams A;
+	memset(&A, 0, sizeof(A));
+	if (ang) {
+		REQUIRE(c, c->ardf_words == (size_t)R.ncomp * R.ncomp * c->rdf_bins * c->ardf_abins, "the component set changed since ls1hip_rdf_config_angular");
+		A.abins = c->ardf_abins;
+		A.aw = 2. / c->ardf_abins;  // RDF.cpp:52
+		A.pair_words = (uint32_t)(c->rdf_bins * c->ardf_abins);
+		A.words = (uint32_t)c->ardf_words;
+		A.g_ardf = c->d_ardf;
+	}
 	{
 		TimedScope ts(c, c->t_rdf);
-		if (!launch_rdf(P, R, c->h_ct.has_rot != 0, mean_per_cell(c), c->stream))
-			FAIL(c, LS1HIP_EINVAL, "the RDF pass could not be launched for this grid");
+		const bool rot = c->h_ct.has_rot != 0;
+		if (!ang || sw) {
+			if (!launch_rdf(P, R, rot, mean_per_cell(c), c->stream)) FAIL(c, LS1HIP_EINVAL, "the RDF pass could not be launched for this grid");
+		}
+		if (ang && !launch_ardf(P, R, A, sw == 0, rot, mean_per_cell(c), c->stream))
+			FAIL(c, LS1HIP_EINVAL, "the angular RDF pass could not be launched for this grid");
 	}
 	HIPCHK(c, hipGetLastError());
 	c->rdf_samples++;  // RDF::tickRDF
@@ -132,11 +173,24 @@ extern "C" int ls1hip_rdf_read(ls1hip_ctx* c, uint64_t* mol, size_t cap_mol, uin
 	return LS1HIP_OK;
 }
 
+extern "C" int ls1hip_rdf_angular_read(ls1hip_ctx* c, uint64_t* ardf, size_t cap, size_t* words) {
+	if (!c) return LS1HIP_EINVAL;
+	REQUIRE(c, c->ardf_abins > 1 && c->d_ardf, "the angular RDF is not configured (ls1hip_rdf_config_angular)");
+	if (words) *words = c->ardf_words;
+	if (!ardf) return LS1HIP_OK;
+	REQUIRE(c, cap >= c->ardf_words, "angular histogram buffer too small: %zu < %zu words", cap, c->ardf_words);
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(ardf, c->d_ardf, c->ardf_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return LS1HIP_OK;
+}
+
 extern "C" int ls1hip_rdf_reset(ls1hip_ctx* c) {
 	if (!c) return LS1HIP_EINVAL;
 	REQUIRE(c, c->rdf_bins > 0 && c->d_rdf, "RDF sampling is not configured (ls1hip_rdf_config)");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipMemsetAsync(c->d_rdf, 0, (c->rdf_mol_words + c->rdf_site_words + MAXC) * sizeof(unsigned long long), c->stream));
+	if (c->d_ardf) HIPCHK(c, hipMemsetAsync(c->d_ardf, 0, c->ardf_words * sizeof(unsigned long long), c->stream));
 	c->rdf_samples = 0;
 	return LS1HIP_OK;
 }

@@ -261,6 +261,17 @@ struct RdfParams {
 	unsigned long long *g_mol, *g_site, *g_n;  // global histograms, owned molecules per component
 };
 
+// angular RDF (kernels_ardf.hip): io/RDF.h:93-109, adapter/RDFCellProcessor.cpp:36-41; bins, dr, maxd2, rc2, ids and the molecule
+// histogram come with the RdfParams of the same sample
+struct ArdfParams {
+	int abins;            // angular bins A > 1
+	double aw;            // 2. / A as RDF::init forms it (RDF.cpp:52)
+	uint32_t pair_words;  // bins * A: words of one ordered component pair
+	uint32_t words;       // ncomp * ncomp * bins * A
+	int hist_lds;         // ARDF words kept in LDS per workgroup (else global atomics): the budget rule of launch_ardf
+	unsigned long long* g_ardf;  // [c_central][c_other][b * A + a]
+};
+
 // orientation distribution functions (kernels_odf.hip): io/ODF.cpp:123-331, adapter/ODFCellProcessor.cpp
 struct OdfParams {
 	int P, G;           // phi1 = phi2 increments, gamma increments
@@ -577,6 +588,10 @@ struct ls1hip_ctx {
 	size_t rdf_mol_words = 0, rdf_site_words = 0;
 	uint64_t rdf_samples = 0;
 	long opt_rdf_every = 0;
+	// its angular part (ls1hip_rdf_config_angular; kernels_ardf.hip): ardf_abins > 1 = on, a buffer of its own
+	int ardf_abins = 0;
+	unsigned long long* d_ardf = nullptr;
+	size_t ardf_words = 0;
 	unsigned long run_step = 0;  // steps ls1hip_run has done on this context (simstep of RDF::afterForces)
 	ls1::Timer t_rdf;
 	// orientation distribution functions (ls1hip_odf_*; kernels_odf.hip): one device buffer of four arrays (11 12 21 22) of odf_words
@@ -786,6 +801,9 @@ bool launch_force_ms_list(const ForceParams& p, bool has_rot, bool lj_only, bool
 						  const double* shift27, double* pk, hipStream_t s, uint32_t* nblocks, size_t partials_cap, bool pk_fresh = false);
 // RDF sampling pass over all bricks (kernels_rdf.hip); fills r.mol_lds / r.site_lds; false: the grid cannot be served (hw != 1)
 bool launch_rdf(const ForceParams& p, RdfParams r, bool has_rot, double mean_per_cell, hipStream_t s);
+// angular RDF sampling pass over all bricks (kernels_ardf.hip); mol: bin the molecule histogram and the component counters of r in
+// the same walk; fills r.mol_lds / a.hist_lds; false: the grid cannot be served (hw != 1)
+bool launch_ardf(const ForceParams& p, RdfParams r, ArdfParams a, bool mol, bool has_rot, double mean_per_cell, hipStream_t s);
 // ODF sampling pass over all bricks (kernels_odf.hip); fills o.hist_lds; false: the grid cannot be served (hw != 1)
 bool launch_odf(const ForceParams& p, OdfParams o, bool has_rot, double mean_per_cell, hipStream_t s);
 size_t odf_lds_words();  // most u32 words (4 W) a workgroup keeps in LDS (above it: global atomics)

@@ -454,6 +454,8 @@ def rdf_collect(engine, dist=None, group=None, device=None):
     import torch
 
     parts = [local["mol"].reshape(-1)] + [b.reshape(-1) for b in local["site"]] + [local["n_per_component"]]
+    if "ardf" in local:  # RDF.cpp:253-272
+        parts.append(local["ardf"].reshape(-1))
     flat = np.concatenate(parts).astype(np.int64)
     t = torch.from_numpy(flat)
     if device is not None:
@@ -470,6 +472,9 @@ def rdf_collect(engine, dist=None, group=None, device=None):
         at += b.size
     out["site"] = site
     out["n_per_component"] = flat[at:at + local["n_per_component"].size].copy()
+    at += local["n_per_component"].size
+    if "ardf" in local:
+        out["ardf"] = flat[at:at + local["ardf"].size].reshape(local["ardf"].shape)
     return out
 
 

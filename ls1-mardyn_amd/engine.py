@@ -26,6 +26,7 @@ class DeviceEngine:
         self.has_rot = False
         self.n_sites = []
         self.rdf_bins = 0
+        self.rdf_angular_bins = 0
         self.widom_slabs = 0
 
     # -- lifetime ---------------------------------------------------------------------------------------------------
@@ -327,6 +328,12 @@ class DeviceEngine:
         """bins = 0 switches the sampling off and frees the device histograms."""
         self._chk(self.lib.ls1hip_rdf_config(self.ctx, int(bins), float(interval_length), int(bool(site_rdf))))
         self.rdf_bins = int(bins)
+        self.rdf_angular_bins = 0  # ls1hip_rdf_config drops the angular part
+
+    def rdf_config_angular(self, angularbins: int):
+        """The angular RDF on top of rdf_config (<angularbins> of the reference's RDF plugin); angularbins <= 1 switches it off."""
+        self._chk(self.lib.ls1hip_rdf_config_angular(self.ctx, int(angularbins)))
+        self.rdf_angular_bins = int(angularbins) if angularbins > 1 else 0
 
     def rdf_layout(self):
         a = C.c_size_t(); b = C.c_size_t()
@@ -340,7 +347,8 @@ class DeviceEngine:
     def rdf_read(self):
         """LOCAL counts of this rank: mol uint64 [pairs, bins] (pairs (i, j >= i) in the order of RDF::collectRDF), site = list of
         uint64 [n_i, n_j, bins] blocks of the pairs with n_i + n_j > 2 (their (i, j) in site_pairs; empty with site_rdf off),
-        n_per_component, samples."""
+        n_per_component, samples; while the angular part is configured also ardf uint64 [nC, nC, bins, A], first index = component
+        of the central molecule."""
         mw, sw = self.rdf_layout()
         bins = self.rdf_bins
         ns = self.n_sites
@@ -357,7 +365,14 @@ class DeviceEngine:
                         blocks.append(site[at:at + n].reshape(ns[i], ns[j], bins))
                         pairs.append((i, j))
                         at += n
-        return dict(mol=mol.reshape(-1, bins), site=blocks, site_pairs=pairs, n_per_component=npc, samples=int(smp.value))
+        out = dict(mol=mol.reshape(-1, bins), site=blocks, site_pairs=pairs, n_per_component=npc, samples=int(smp.value))
+        if self.rdf_angular_bins:
+            n = C.c_size_t()
+            ardf = np.zeros(len(ns) * len(ns) * bins * self.rdf_angular_bins, dtype=np.uint64)
+            self._chk(self.lib.ls1hip_rdf_angular_read(self.ctx, ardf.ctypes.data_as(capi._u64p), ardf.size, C.byref(n)))
+            assert n.value == ardf.size
+            out["ardf"] = ardf.reshape(len(ns), len(ns), bins, self.rdf_angular_bins)
+        return out
 
     def rdf_reset(self):
         self._chk(self.lib.ls1hip_rdf_reset(self.ctx))

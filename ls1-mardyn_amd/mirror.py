@@ -476,6 +476,99 @@ def _g6(x) -> str:
     return "%.6g" % x
 
 
+class ARDF(RDF):
+    """The RDF plugin with <angularbins> > 1 (RDF.cpp:49-55): molecule histogram, counters and the angular histograms
+    [c_central][c_other][b * A + a] of ONE device traversal; site histograms are off.  endStep writes the .ardf files of every
+    ordered component pair (RDF.cpp:361-370); the .rdf files stay with mirror.RDF."""
+
+    def __init__(self, components: ComponentSet, cutoffRadius: float, *, bins: int = 1, intervallength: float = 1.0, angularbins: int = 2,
+                 writefrequency: int = 1, samplingfrequency: int = 1, outputprefix: str = "mardyn"):
+        if angularbins <= 1:
+            raise ValueError("angularbins must be > 1 (mirror.RDF is the plugin without the angular part)")
+        self._angularBins = int(angularbins)
+        self._angularIntervalLength = 2. / self._angularBins
+        super().__init__(components, cutoffRadius, writefrequency=writefrequency, samplingfrequency=samplingfrequency,
+                         outputprefix=outputprefix, bins=bins, intervallength=intervallength)
+        self._doCollectSiteRDF = False
+        self._globalAccumulatedSiteDistribution = {}
+        nC = self._numberOfComponents
+        self._globalAccumulatedARDFDistribution = np.zeros((nC, nC, self._bins * self._angularBins), dtype=np.uint64)
+        self._zero_current()
+
+    def _zero_current(self):
+        super()._zero_current()
+        nC = self._numberOfComponents
+        self._ARDFdistribution_global = np.zeros((nC, nC, self._bins * self._angularBins), dtype=np.uint64)
+
+    def _configure(self, engine: DeviceEngine):
+        if self._engine is not engine:
+            engine.rdf_config(self._bins, self._intervalLength, False)
+            engine.rdf_config_angular(self._angularBins)
+            self._engine = engine
+
+    def setGlobal(self, counts):
+        super().setGlobal(counts)
+        nC = self._numberOfComponents
+        self._ARDFdistribution_global = np.asarray(counts["ardf"], dtype=np.uint64).reshape(nC, nC, -1).copy()
+
+    # --- RDF::accumulateRDF, RDF.cpp:221-228
+    def accumulateRDF(self):
+        if self._numberOfRDFTimesteps <= 0:
+            return
+        super().accumulateRDF()
+        self._globalAccumulatedARDFDistribution += self._ARDFdistribution_global
+
+    def endStep(self, particleContainer, domainDecomp, domain: Domain, simStep: int, directory: str = "."):
+        import os
+
+        if self._numberOfRDFTimesteps <= 0:
+            return
+        if simStep > 0 and simStep % self._writeFrequency == 0:
+            self.collectRDF(domainDecomp)
+            if (domainDecomp.getRank() if hasattr(domainDecomp, "getRank") else 0) == 0:
+                self.accumulateRDF()
+                for i in range(self._numberOfComponents):
+                    for j in range(self._numberOfComponents):
+                        self.writeToFileARDF(domain, os.path.join(directory, "%s_%d-%d.%09d.ardf" % (self._outputPrefix, i, j, simStep)), i, j)
+            self.reset()
+
+    # --- RDF::writeToFileARDF, RDF.cpp:377-453 (the stream keeps its default precision of 6)
+    def writeToFileARDF(self, domain: Domain, filename: str, i: int, j: int):
+        V = domain.getGlobalVolume()
+        nT, nA = self._numberOfRDFTimesteps, self._accumulatedNumberOfRDFTimesteps
+        N_i, N_Ai = _div(int(self._globalCtr[i]), nT), _div(int(self._globalAccumulatedCtr[i]), nA)
+        N_j, N_Aj = _div(int(self._globalCtr[j]), nT), _div(int(self._globalAccumulatedCtr[j]), nA)
+        out = ["\n# \n# ctr_i: %d\n# ctr_j: %d\n# V: %s\n# _universalRDFTimesteps: %d\n# _universalAccumulatedTimesteps: %d"
+               "\n# _samplingFrequency: %d\n# rho_i: %s (acc. %s)\n# rho_j: %s (acc. %s)\n# \n"
+               % (int(self._globalCtr[i]), int(self._globalCtr[j]), _g6(V), nT, nA, self._samplingFrequency, _g6(N_i / V), _g6(N_Ai / V),
+                  _g6(N_j / V), _g6(N_Aj / V)),
+               "#r\tcos(phi)\tcounter\tardf\tardf_{integral}\tacc_rdf acc_rdf_{integral}\t\tdV\tNpair(curr.)\tNpair(accu.)\t\t"
+               "normalization(curr.)\tnormalization(accu.)\n"]
+        cur, acc = self._ARDFdistribution_global[i, j], self._globalAccumulatedARDFDistribution[i, j]
+        same = (N_i * (N_i - 1.0), N_Ai * (N_Ai - 1.0)) if i == j else (N_i * N_j, N_Ai * N_Aj)
+        w, aw, A = self._intervalLength, self._angularIntervalLength, self._angularBins
+        N_pair_int = N_Apair_int = 0.0
+        for l in range(self._bins * A):
+            radialID, angularID = divmod(l, A)
+            rmin, rmid, rmax = radialID * w, (radialID + 0.5) * w, (radialID + 1.0) * w
+            cosPhiMin, cosPhiMid, cosPhiMax = 1. - angularID * aw, 1. - (angularID + 0.5) * aw, 1. - (angularID + 1.0) * aw
+            r3min, r3max = rmin * rmin * rmin, rmax * rmax * rmax
+            dV = 2. / 3. * np.pi * ((r3max - r3min) * (1. - cosPhiMax) + (r3min - r3max) * (1. - cosPhiMin))
+            N_pair = _div(int(cur[l]), nT)
+            N_pair_int += N_pair
+            N_Apair = _div(int(acc[l]), nA)
+            N_Apair_int += N_Apair
+            cone = r3min + 0.5 * ((r3max - r3min) * (1 - cosPhiMax))
+            N_pair_norm, N_Apair_norm = same[0] * dV / V, same[1] * dV / V
+            N_pair_int_norm, N_Apair_int_norm = same[0] * 4.1887902 * cone / V, same[1] * 4.1887902 * cone / V
+            out.append("%s\t%s\t%d\t%s %s\t%s %s\t\t%s\t%s\t%s\t\t%s\t%s\n" % (
+                _g6(rmid), _g6(cosPhiMid), int(cur[l]), _g6(_div(N_pair, N_pair_norm)), _g6(_div(N_pair_int, N_pair_int_norm)),
+                _g6(_div(N_Apair, N_Apair_norm)), _g6(_div(N_Apair_int, N_Apair_int_norm)), _g6(dV), _g6(N_pair), _g6(N_Apair),
+                _g6(N_pair_norm), _g6(N_Apair_norm)))
+        with open(filename, "w") as f:
+            f.write("".join(out))
+
+
 class CavityWriter:
     """The reference's CavityWriter plugin (io/CavityWriter.{h,cpp}) over the device pass: keyword arguments = the nodes
     CavityWriter::readXML reads (CavityWriter.cpp:18-111); ControlVolume = (x0, x1, y0, y1, z0, z1) or None (the whole domain);
